@@ -565,6 +565,26 @@ int trid_colnorm_bwd_f32(const float* dpnt, const float* pnt, const float* inv_n
  * softplus terms * 2/B. */
 int trid_global_align_rows_f32(float* S, const int64_t* ids, float* loss_rows, int B, int ldS, float alpha,
                                float beta, float scale_pos, float scale_neg, float gscale, void* stream);
+/* CMPM rows (losses.py:156-203).  S [B, ldS]: v @ normalize(t)^T (or its mirror image); only the first B columns of a
+ * row enter the softmax.  loss_rows[i] = sum_j p_ij (log p_ij - log(q_ij + epsilon)), q the same-id mask over its row
+ * norm; in place S <- gscale * dloss_i/dS_ij. */
+int trid_cmpm_rows_f32(float* S, const int64_t* ids, float* loss_rows, int B, int ldS, float epsilon, float gscale,
+                       void* stream);
+/* out2[0] / out2[1] = mean of row_scale[i]*S[i,j] over the same-id / different-id pairs (losses.py:196-200: the
+ * `verbose` figures of cmpm_loss); row_scale may be NULL; an empty set gives NaN */
+int trid_pair_sim_means_f32(const float* S, const float* row_scale, const int64_t* ids, float* out2, int B, int ldS,
+                            void* stream);
+/* CMPC operand (losses.py:73-82): X[i] = (v_i . t^_i) t^_i, X[B+i] = (t_i . v^_i) v^_i ([2B, C], the logit GEMM's left
+ * operand); dots [2B] the two row dots, inv [2B] = 1/|v_i|, 1/|t_i| */
+int trid_cross_project_rows_f32(const float* v, const float* t, float* X, float* dots, float* inv, int B, int C,
+                                void* stream);
+/* ... and its backward: G [2B, C] = dL/dX -> dv, dt [B, C] (both contributions of each, normalisation included) */
+int trid_cross_project_rows_bwd_f32(const float* G, const float* v, const float* t, const float* dots, const float* inv,
+                                    float* dv, float* dt, int B, int C, void* stream);
+/* idx[r] = argmax_j x[r, j] over the first n of ld columns (ties: lowest index, as torch.argmax, losses.py:92-93);
+ * hit[r] = 1.0 if that equals labels[r] (losses.py:95-96).  idx or hit may be NULL; labels only with hit. */
+int trid_argmax_rows_f32(const float* x, const int64_t* labels, int64_t* idx, float* hit, long long rows, int n, int ld,
+                         void* stream);
 /* out = g3[0]*a + g3[1]*b + g3[2]*c, g3 device-resident upstream gradients (b, c may be NULL) */
 int trid_axpby3_f32(float* out, const float* a, const float* b, const float* c, const float* g3, long long n,
                     void* stream);

@@ -143,3 +143,11 @@ def moco_cfg(visual="m_resnet50", K=2048, height=384, width=128, num_classes=110
     cfg.SOLVER.IMS_PER_BATCH = 128
     cfg.SOLVER.BASE_LR = 0.0001
     return cfg
+
+
+def baseline_cfg(visual="m_resnet50", height=384, width=128, num_classes=11003):
+    """The shipped ``baseline_gru_clip{rn50,rn101}_ls_bs128.yaml`` settings: the MoCo configs' encoders under
+    ``EMBED_HEAD: 'simple'`` (no queue, no key encoders)."""
+    cfg = moco_cfg(visual, height=height, width=width, num_classes=num_classes)
+    cfg.MODEL.EMBEDDING.EMBED_HEAD = "simple"
+    return cfg

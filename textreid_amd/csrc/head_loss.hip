@@ -1,7 +1,8 @@
 // Embedding head and loss kernels: L2 row normalisation, the batch-wide queue
 // hit mask, masked InfoNCE rows, label-smoothed cross-entropy rows, projection
-// column normalisation, global-align softplus terms, small reductions.
-// Reference: head.py:126-175, losses.py:6-62,102-128,206-217, moco_head/loss.py.
+// column normalisation, global-align softplus terms, CMPM rows, the CMPC cross
+// projection, small reductions.
+// Reference: head.py:126-175, losses.py:6-217, moco_head/loss.py.
 // The [rows, K] similarity / logit matrices are produced by trid_gemm_f32; the
 // kernels here turn them into per-row losses and, in place, into dL/dlogits, so
 // that the backward pass is two more GEMMs and no second softmax.
@@ -333,6 +334,248 @@ __global__ __launch_bounds__(256) void global_align_rows_kernel(float* __restric
     if (threadIdx.x == 0) loss_rows[i] = acc * 2.f / (float)B;
 }
 
+// CMPM rows (losses.py:156-203): one wavefront per row of the projection matrix S [B, ldS] (only the first B columns
+// enter the softmax: the zero padding of the GEMM operands stays out).  p = softmax(row), target q_ij = [id_i == id_j] /
+// sqrt(n_i) with n_i the number of row i's same-id columns.  (The reference divides element [i,j] by the norm of mask
+// row j, a [B] vector broadcast along the last axis; the mask is non-zero only where id_i == id_j, and equal ids have
+// equal counts, so that is the per-row form computed here.)  loss_i = sum_j p_ij (log p_ij - log(q_ij + eps));
+// in place S_ij <- gs * p_ij ((log p_ij - log(q_ij + eps)) - loss_i) = gs * dloss_i/dS_ij.
+// B <= 256: the row lives in four registers per lane; longer rows are re-read (L2-resident) in each pass.
+__global__ __launch_bounds__(256) void cmpm_rows_kernel(float* __restrict__ S, const int64_t* __restrict__ ids,
+                                                        float* __restrict__ loss_rows, int B, int ldS, float eps,
+                                                        float gs) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= B) return;  // (whole wavefronts leave: no partial-wave shuffles below)
+    float* r = S + (long long)i * ldS;
+    const int64_t idi = ids[i];
+    const bool inreg = B <= 256;
+    float v[4];
+    unsigned same = 0;  // bit k: column lane + 64 k carries row i's id (register path)
+    float m = -INFINITY, cnt = 0.f;
+    if (inreg) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = lane + 64 * k;
+            v[k] = j < B ? r[j] : -INFINITY;
+            if (j < B && ids[j] == idi) same |= 1u << k;
+            m = fmaxf(m, v[k]);
+        }
+        cnt = (float)__popc(same);
+    } else {
+        for (int j = lane; j < B; j += 64) {
+            m = fmaxf(m, r[j]);
+            cnt += ids[j] == idi ? 1.f : 0.f;
+        }
+    }
+    m = wave_max(m);
+    cnt = wave_sum(cnt);
+    float l = 0.f;
+    if (inreg) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) l += expf(v[k] - m);  // exp(-inf) = 0 for the columns past B
+    } else {
+        for (int j = lane; j < B; j += 64) l += expf(r[j] - m);
+    }
+    l = wave_sum(l);
+    const float lse = m + logf(l);
+    const float lq_same = logf(1.f / sqrtf(cnt) + eps), lq_diff = logf(eps);
+    float acc = 0.f;
+    if (inreg) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (lane + 64 * k < B) {
+                const float lp = v[k] - lse;
+                acc += expf(lp) * (lp - ((same >> k) & 1u ? lq_same : lq_diff));
+            }
+        }
+    } else {
+        for (int j = lane; j < B; j += 64) {
+            const float lp = r[j] - lse;
+            acc += expf(lp) * (lp - (ids[j] == idi ? lq_same : lq_diff));
+        }
+    }
+    const float loss = wave_sum(acc);
+    if (inreg) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = lane + 64 * k;
+            if (j < B) {
+                const float lp = v[k] - lse;
+                r[j] = gs * expf(lp) * ((lp - ((same >> k) & 1u ? lq_same : lq_diff)) - loss);
+            }
+        }
+    } else {
+        for (int j = lane; j < B; j += 64) {
+            const float lp = r[j] - lse;
+            r[j] = gs * expf(lp) * ((lp - (ids[j] == idi ? lq_same : lq_diff)) - loss);
+        }
+    }
+    if (lane == 0) loss_rows[i] = loss;
+}
+
+// mean of row_scale[i] * S[i,j] over the same-id pairs and over the different-id pairs (cmpm_loss's `verbose` figures,
+// losses.py:196-200): one workgroup, fixed summation order.  An empty set gives 0/0 = NaN, as torch.mean of nothing.
+__global__ __launch_bounds__(256) void pair_sim_means_kernel(const float* __restrict__ S, const float* __restrict__ row_scale,
+                                                             const int64_t* __restrict__ ids, float* __restrict__ out2,
+                                                             int B, int ldS) {
+    __shared__ float red[8];
+    float sp = 0.f, sn = 0.f, np = 0.f;
+    for (int e = threadIdx.x; e < B * B; e += 256) {
+        const int i = e / B, j = e - i * B;
+        const float s = S[(long long)i * ldS + j] * (row_scale != nullptr ? row_scale[i] : 1.f);
+        if (ids[i] == ids[j]) {
+            sp += s;
+            np += 1.f;
+        } else {
+            sn += s;
+        }
+    }
+    sp = block_sum(sp, red);
+    sn = block_sum(sn, red);
+    np = block_sum(np, red);
+    if (threadIdx.x == 0) {
+        out2[0] = sp / np;
+        out2[1] = sn / ((float)B * (float)B - np);
+    }
+}
+
+// CMPC operand (losses.py:73-82): one wavefront per pair i.  With d = <v_i, t_i>, iv = 1/max(|v_i|, 1e-12) and it
+// likewise: ipt_i = (v_i . t^_i) t^_i = (d it) it t_i -> X[i], tpi_i = (t_i . v^_i) v^_i = (d iv) iv v_i -> X[B + i];
+// dots[i] = v_i . t^_i, dots[B + i] = t_i . v^_i, inv[i] = iv, inv[B + i] = it.  VEC: 128-bit accesses (C % 4 == 0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void cross_project_rows_kernel(const float* __restrict__ v, const float* __restrict__ t,
+                                                                 float* __restrict__ X, float* __restrict__ dots,
+                                                                 float* __restrict__ inv, int B, int C) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= B) return;
+    const float* vr = v + (long long)i * C;
+    const float* tr = t + (long long)i * C;
+    float vv = 0.f, tt = 0.f, vt = 0.f;
+    if (VEC) {
+        for (int c = 4 * lane; c < C; c += 256) {
+            const float4 a = *reinterpret_cast<const float4*>(vr + c), b = *reinterpret_cast<const float4*>(tr + c);
+            vv += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+            tt += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+            vt += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) {
+            vv = fmaf(vr[c], vr[c], vv);
+            tt = fmaf(tr[c], tr[c], tt);
+            vt = fmaf(vr[c], tr[c], vt);
+        }
+    }
+    vv = wave_sum(vv);
+    tt = wave_sum(tt);
+    vt = wave_sum(vt);
+    const float iv = 1.f / fmaxf(sqrtf(vv), 1e-12f), it = 1.f / fmaxf(sqrtf(tt), 1e-12f);
+    const float a = vt * it, b = vt * iv;
+    float* x1 = X + (long long)i * C;
+    float* x2 = X + (long long)(B + i) * C;
+    if (VEC) {
+        const float s1 = a * it, s2 = b * iv;
+        for (int c = 4 * lane; c < C; c += 256) {
+            const float4 p = *reinterpret_cast<const float4*>(vr + c), q = *reinterpret_cast<const float4*>(tr + c);
+            *reinterpret_cast<float4*>(x1 + c) = make_float4(s1 * q.x, s1 * q.y, s1 * q.z, s1 * q.w);
+            *reinterpret_cast<float4*>(x2 + c) = make_float4(s2 * p.x, s2 * p.y, s2 * p.z, s2 * p.w);
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) {
+            x1[c] = a * it * tr[c];
+            x2[c] = b * iv * vr[c];
+        }
+    }
+    if (lane == 0) {
+        dots[i] = a;
+        dots[B + i] = b;
+        inv[i] = iv;
+        inv[B + i] = it;
+    }
+}
+
+// Backward of the above.  G [2B, C] = dL/dX.  With g1 = G[i], g2 = G[B + i], a = dots[i], b = dots[B + i],
+// p1 = g1 . t^, p2 = g2 . v^:
+//   through ipt:  dv  = p1 t^;   dt^ = a g1 + p1 v, and the normalisation's Jacobian (dt^ - t^ <dt^, t^>) it with
+//                 <dt^, t^> = a p1 + p1 (v . t^) = 2 a p1;
+//   through tpi:  dt  = p2 v^;   dv^ = b g2 + p2 t, <dv^, v^> = 2 b p2, Jacobian likewise.
+// Each modality receives two contributions, summed in that fixed order (ipt's first).
+__global__ __launch_bounds__(256) void cross_project_rows_bwd_kernel(const float* __restrict__ G, const float* __restrict__ v,
+                                                                     const float* __restrict__ t,
+                                                                     const float* __restrict__ dots,
+                                                                     const float* __restrict__ inv, float* __restrict__ dv,
+                                                                     float* __restrict__ dt, int B, int C) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= B) return;
+    const float* vr = v + (long long)i * C;
+    const float* tr = t + (long long)i * C;
+    const float* g1 = G + (long long)i * C;
+    const float* g2 = G + (long long)(B + i) * C;
+    const float a = dots[i], b = dots[B + i], iv = inv[i], it = inv[B + i];
+    float p1 = 0.f, p2 = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        p1 = fmaf(g1[c], tr[c], p1);
+        p2 = fmaf(g2[c], vr[c], p2);
+    }
+    p1 = wave_sum(p1) * it;
+    p2 = wave_sum(p2) * iv;
+    for (int c = lane; c < C; c += 64) {
+        const float vn = vr[c] * iv, tn = tr[c] * it;
+        const float dv1 = p1 * tn;
+        const float dt1 = (a * g1[c] + p1 * vr[c] - 2.f * a * p1 * tn) * it;
+        const float dt2 = p2 * vn;
+        const float dv2 = (b * g2[c] + p2 * tr[c] - 2.f * b * p2 * vn) * iv;
+        dv[(long long)i * C + c] = dv1 + dv2;
+        dt[(long long)i * C + c] = dt1 + dt2;
+    }
+}
+
+// one workgroup per row: index of the row maximum (ties: the lowest index, as torch.argmax); hit[r] = 1 if it equals
+// labels[r] (both outputs optional)
+__global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, const int64_t* __restrict__ labels,
+                                                          int64_t* __restrict__ idx, float* __restrict__ hit, int n,
+                                                          int ld) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const long long row = blockIdx.x;
+    const float* r = x + row * ld;
+    float best = -INFINITY;
+    int at = n;  // (every index beats n: an all -inf row answers 0 through the scan below)
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const float s = r[j];
+        if (s > best || (s == best && j < at)) {
+            best = s;
+            at = j;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oa = __shfl_xor(at, o, 64);
+        if (ob > best || (ob == best && oa < at)) {
+            best = ob;
+            at = oa;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        bv[threadIdx.x >> 6] = best;
+        bi[threadIdx.x >> 6] = at;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < at)) {
+                best = bv[w];
+                at = bi[w];
+            }
+        if (at >= n) at = 0;
+        if (idx != nullptr) idx[row] = at;
+        if (hit != nullptr) hit[row] = (int64_t)at == labels[row] ? 1.f : 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ x, float* __restrict__ out, long long n,
                                                   float scale, int accumulate) {
     __shared__ float red[8];
@@ -475,6 +718,50 @@ extern "C" int trid_global_align_rows_f32(float* S, const int64_t* ids, float* l
     hipLaunchKernelGGL(global_align_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, S, ids, loss_rows, B, ldS,
                        alpha, beta, scale_pos, scale_neg, gscale * 2.f / (float)B);
     return check_launch("trid_global_align_rows_f32");
+}
+
+extern "C" int trid_cmpm_rows_f32(float* S, const int64_t* ids, float* loss_rows, int B, int ldS, float epsilon,
+                                  float gscale, void* stream) {
+    TRID_REQUIRE(S && ids && loss_rows && B > 0 && ldS >= B && epsilon > 0.f, "trid_cmpm_rows_f32: bad arguments");
+    hipLaunchKernelGGL(cmpm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, ids, loss_rows, B, ldS,
+                       epsilon, gscale);
+    return check_launch("trid_cmpm_rows_f32");
+}
+
+extern "C" int trid_pair_sim_means_f32(const float* S, const float* row_scale, const int64_t* ids, float* out2, int B,
+                                       int ldS, void* stream) {
+    TRID_REQUIRE(S && ids && out2 && B > 0 && B <= 16384 && ldS >= B, "trid_pair_sim_means_f32: bad arguments");
+    hipLaunchKernelGGL(pair_sim_means_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, S, row_scale, ids, out2, B, ldS);
+    return check_launch("trid_pair_sim_means_f32");
+}
+
+extern "C" int trid_cross_project_rows_f32(const float* v, const float* t, float* X, float* dots, float* inv, int B, int C,
+                                           void* stream) {
+    TRID_REQUIRE(v && t && X && dots && inv && B > 0 && C > 0, "trid_cross_project_rows_f32: bad arguments");
+    const bool vec = (C & 3) == 0 && aligned16(v) && aligned16(t) && aligned16(X);
+    if (vec)
+        hipLaunchKernelGGL(cross_project_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, v, t, X,
+                           dots, inv, B, C);
+    else
+        hipLaunchKernelGGL(cross_project_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, v, t, X,
+                           dots, inv, B, C);
+    return check_launch("trid_cross_project_rows_f32");
+}
+
+extern "C" int trid_cross_project_rows_bwd_f32(const float* G, const float* v, const float* t, const float* dots,
+                                               const float* inv, float* dv, float* dt, int B, int C, void* stream) {
+    TRID_REQUIRE(G && v && t && dots && inv && dv && dt && B > 0 && C > 0, "trid_cross_project_rows_bwd_f32: bad arguments");
+    hipLaunchKernelGGL(cross_project_rows_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, G, v, t, dots,
+                       inv, dv, dt, B, C);
+    return check_launch("trid_cross_project_rows_bwd_f32");
+}
+
+extern "C" int trid_argmax_rows_f32(const float* x, const int64_t* labels, int64_t* idx, float* hit, long long rows, int n,
+                                    int ld, void* stream) {
+    TRID_REQUIRE(x && (idx || hit) && (labels || !hit) && rows > 0 && n > 0 && ld >= n, "trid_argmax_rows_f32: bad arguments");
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, labels, idx, hit, n,
+                       ld);
+    return check_launch("trid_argmax_rows_f32");
 }
 
 extern "C" int trid_sum_f32(const float* x, float* out, long long n, float scale, int accumulate, void* stream) {

@@ -22,7 +22,8 @@ def compute_on_dataset(model, data_loader, device, dedupe=True, encode_batch=512
     encoder's M = B x 192-row launches of layer3 / layer4 fill the chip from ~256 images on (16.2 k imgs/s at 128 per
     pass, 18.0 k at 512 - DESIGN section 8).  0 / None: one encoder pass per loader batch, as the reference."""
     model.eval()
-    head = model.embed_model
+    # the MoCo head owns its encoders; with any other head the model runs them (Model.encode_images / encode_captions)
+    head = model.embed_model if hasattr(model.embed_model, "encode_images") else model
     dataset = getattr(data_loader, "dataset", None)
     can_dedupe = dedupe and dataset is not None and hasattr(dataset, "get_id_info")
     results, cache = {}, {}

@@ -1,8 +1,10 @@
-"""Losses of the MoCo configs on the HIP kernel library.
+"""Losses on the HIP kernel library.
 
 Same call surface as the reference ``lib/models/losses.py``:
 ``instance_loss`` (:42-62, with ``CrossEntropyLabelSmooth`` :6-39),
-``global_align_loss`` (:102-128) and ``infonce_loss`` (:206-217); plus
+``cmpc_loss`` (:65-99), ``global_align_loss`` (:102-128),
+``global_align_loss_from_sim`` (:131-153), ``cmpm_loss`` (:156-203) and
+``infonce_loss`` (:206-217); plus
 ``queue_infonce_loss``, the fused form the MoCo head uses (queue similarity +
 batch-wide negative filter + InfoNCE, reference head.py:148-170 followed by
 losses.py:206-217) that never builds the gathered negative matrices.
@@ -120,6 +122,151 @@ class _GlobalAlignFn(torch.autograd.Function):
 def global_align_loss(visual_embed, textual_embed, labels, alpha=0.6, beta=0.4, scale_pos=10, scale_neg=40):
     _check(visual_embed, textual_embed, labels)
     return _GlobalAlignFn.apply(visual_embed, textual_embed, labels, alpha, beta, scale_pos, scale_neg)
+
+
+class _GlobalAlignFromSimFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, similarity, labels, alpha, beta, scale_pos, scale_neg):
+        B = labels.shape[0]
+        S = similarity.detach().clone(memory_format=torch.contiguous_format)  # the caller's matrix is not modified
+        rows = ops.empty((B,), S)
+        lab = labels.long().contiguous()
+        call("trid_global_align_rows_f32", _p(S), _p(lab), _p(rows), B, S.stride(0), float(alpha), float(beta),
+             float(scale_pos), float(scale_neg), 1.0, stream())
+        loss = ops.empty((1,), S)
+        ops.sum_to(rows, loss, 1.0)
+        ctx.saved = S
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dS = ctx.saved
+        ctx.saved = None
+        return _scaled(g, dS), None, None, None, None, None
+
+
+def global_align_loss_from_sim(similarity, labels, alpha=0.6, beta=0.4, scale_pos=10, scale_neg=40):
+    """lib/models/losses.py:131-153: the global-align terms of a [B,B] similarity matrix the caller built."""
+    _check(similarity, labels)
+    if similarity.dim() != 2 or similarity.shape[0] != labels.shape[0] or similarity.shape[1] != labels.shape[0]:
+        raise RuntimeError("global_align_loss_from_sim: similarity must be [B,B] for B labels")
+    return _GlobalAlignFromSimFn.apply(similarity, labels, alpha, beta, scale_pos, scale_neg)
+
+
+def _pad_rows(x, Bp):
+    if x.shape[0] == Bp:
+        return x
+    xp = torch.zeros(Bp, x.shape[1], device=x.device)
+    xp[: x.shape[0]].copy_(x)
+    return xp
+
+
+class _CmpmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, t, labels, epsilon, verbose):
+        B, C = v.shape
+        vd, td = v.detach().contiguous(), t.detach().contiguous()
+        vn, inv_v = ops.l2norm_rows(vd)
+        tn, inv_t = ops.l2norm_rows(td)
+        Bp = (B + 3) // 4 * 4  # the [B,B] matrices are GEMM operands later (leading dimension % 4): zero-pad the batch
+        vp, tp, vnp, tnp = (_pad_rows(x, Bp) for x in (vd, td, vn, tn))
+        A = ops.linear(vp, tnp)   # [Bp,Bp] v_i . t^_j  (losses.py:176: the LEFT operand is not normalised)
+        Bm = ops.linear(tp, vnp)  # t_i . v^_j (:177)
+        lab = labels.long().contiguous()
+        sims = None
+        if verbose:  # cosine = A scaled by 1/|v_i|, read before the row kernel overwrites A (:196-200)
+            sims = ops.empty((2,), v)
+            call("trid_pair_sim_means_f32", _p(A), _p(inv_v), _p(lab), _p(sims), B, Bp, stream())
+        rows = ops.empty((2, B), v)
+        # (the padding columns B..Bp stay out of the softmax and keep their zeros: they are columns of the gradient GEMMs)
+        call("trid_cmpm_rows_f32", _p(A), _p(lab), _p(rows[0]), B, Bp, float(epsilon), 1.0 / B, stream())
+        call("trid_cmpm_rows_f32", _p(Bm), _p(lab), _p(rows[1]), B, Bp, float(epsilon), 1.0 / B, stream())
+        loss = ops.empty((1,), v)
+        ops.sum_to(rows.view(-1), loss, 1.0 / B)
+        dv = ops.matmul_nn(A, tnp)[:B]                  # dA @ t^
+        dtn = ops.matmul_tn(A, vp)[:B].contiguous()     # dA^T @ v
+        dt = ops.matmul_nn(Bm, vnp)[:B]
+        dvn = ops.matmul_tn(Bm, tp)[:B].contiguous()
+        ops.l2norm_rows_bwd(dvn, vn, inv_v, dx=dv, accumulate=True)  # fixed order: the direct term, then the normalised one
+        ops.l2norm_rows_bwd(dtn, tn, inv_t, dx=dt, accumulate=True)
+        ctx.saved = (dv, dt)
+        if verbose:
+            ctx.mark_non_differentiable(sims)
+            return loss[0], sims
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        dv, dt = ctx.saved
+        ctx.saved = None
+        return _scaled(g, dv), _scaled(g, dt), None, None, None
+
+
+def cmpm_loss(visual_embed, textual_embed, labels, verbose=False, epsilon=1e-8):
+    """Cross-modal projection matching, lib/models/losses.py:156-203.  ``verbose``: (loss, mean cosine of the same-id
+    pairs, mean cosine of the others), the two figures 0-d device tensors without gradient."""
+    _check(visual_embed, textual_embed, labels)
+    if verbose:
+        loss, sims = _CmpmFn.apply(visual_embed, textual_embed, labels, epsilon, True)
+        return loss, sims[0], sims[1]
+    return _CmpmFn.apply(visual_embed, textual_embed, labels, epsilon, False)
+
+
+class _CmpcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, projection, v, t, labels, verbose):
+        C, N = projection.shape
+        B = v.shape[0]
+        ldn = _pad16(N)
+        proj = projection.detach().contiguous()
+        pnt = ops.empty((ldn, C), v)
+        invn = ops.empty((N,), v)
+        call("trid_colnorm_f32", _p(proj), None, _p(pnt), _p(invn), C, N, ldn, stream())
+        vd, td = v.detach().contiguous(), t.detach().contiguous()
+        X = ops.empty((2 * B, C), v)  # rows 0..B: image projected onto text, B..2B: text projected onto image (:77-82)
+        dots = ops.empty((2 * B,), v)
+        inv = ops.empty((2 * B,), v)
+        call("trid_cross_project_rows_f32", _p(vd), _p(td), _p(X), _p(dots), _p(inv), B, C, stream())
+        logits = ops.linear(X, pnt)  # [2B, ldn]
+        labels2 = torch.cat([labels, labels]).long().contiguous()
+        prec = None
+        if verbose:  # the arg-max is taken before the CE kernel turns the logits into their gradient (:92-96)
+            hit = ops.empty((2, B), v)
+            call("trid_argmax_rows_f32", _p(logits), _p(labels2), None, _p(hit), 2 * B, N, ldn, stream())
+            prec = ops.empty((2,), v)
+            ops.sum_to(hit[0], prec[0:1], 1.0 / B)
+            ops.sum_to(hit[1], prec[1:2], 1.0 / B)
+        rows = ops.empty((2 * B,), v)
+        call("trid_smooth_ce_rows_f32", _p(logits), _p(labels2), _p(rows), 2 * B, N, ldn, 0.0, 1.0 / B, stream())
+        loss = ops.empty((1,), v)
+        ops.sum_to(rows, loss, 1.0 / B)
+        dX = ops.matmul_nn(logits, pnt)
+        dpnt = ops.matmul_tn(logits, X)
+        dproj = ops.empty((C, N), v)
+        call("trid_colnorm_bwd_f32", _p(dpnt), _p(pnt), _p(invn), _p(dproj), C, N, ldn, stream())
+        dv, dt = torch.empty_like(vd), torch.empty_like(td)
+        call("trid_cross_project_rows_bwd_f32", _p(dX), _p(vd), _p(td), _p(dots), _p(inv), _p(dv), _p(dt), B, C, stream())
+        ctx.saved = (dproj, dv, dt)
+        if verbose:
+            ctx.mark_non_differentiable(prec)
+            return loss[0], prec
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        dproj, dv, dt = ctx.saved
+        ctx.saved = None
+        return _scaled(g, dproj), _scaled(g, dv), _scaled(g, dt), None, None
+
+
+def cmpc_loss(projection, visual_embed, textual_embed, labels, verbose=False):
+    """Cross-modal projection classification, lib/models/losses.py:65-99.  ``verbose``: (loss, image precision, text
+    precision), the two figures 0-d device tensors without gradient."""
+    _check(projection, visual_embed, textual_embed, labels)
+    if verbose:
+        loss, prec = _CmpcFn.apply(projection, visual_embed, textual_embed, labels, True)
+        return loss, prec[0], prec[1]
+    return _CmpcFn.apply(projection, visual_embed, textual_embed, labels, False)
 
 
 class _InfoNCEFn(torch.autograd.Function):
