@@ -51,7 +51,7 @@ const char* trid_last_error_string(void);
 enum {
     TRID_A_KC = 0,   /* A[m*lda + k] */
     TRID_A_MC = 1,   /* A[k*lda + m] */
-    TRID_A_CONV = 2, /* A = NHWC image [Bimg,H,W,Cin]; m = pixel, k = (tap,c); 3x3, stride 1, pad 1 */
+    TRID_A_CONV = 2, /* A = NHWC image [Bimg,H,W,Cin]; m = pixel, k = (tap,c); 3x3, stride 1, pad 1 (stride 2: trid_gemm_desc.conv_stride) */
     TRID_B_KC = 0,   /* B[n*ldb + k]  (weights [N,K]) */
     TRID_B_NC = 1,   /* B[k*ldb + n] */
     TRID_B_CONV = 2  /* B = NHWC image; k = pixel, n = (tap,c)  (weight gradient of a 3x3 conv) */
@@ -130,6 +130,18 @@ typedef struct trid_gemm_desc {
     float* bnb_ws2;
     int32_t bnb_relu;
     const void* bnb_mask;    /* bnb_relu == 2: ReLU bits over [M][N], the layout of c_mask */
+    /* trid_gemm_f32 only: stride of the 3x3 gather (0 / 1: stride 1, the kernels as they were; 2: the stride-2 / pad-1
+     * convolutions of the ImageNet ResNet, nn.Conv2d(planes, planes, 3, stride=2, padding=1), resnet.py:62-70).  H, W are ALWAYS
+     * the convolution's INPUT map; the output map is Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1 (odd H, W are legal).
+     *   a_mode TRID_A_CONV, conv_transposed == 0 (forward): A = x [Bimg,H,W,Cin], rows m = OUTPUT pixels (M = Bimg*Ho*Wo),
+     *     tap (ky,kx) of row (b,ho,wo) reads x[b, 2ho-1+ky, 2wo-1+kx].
+     *   a_mode TRID_A_CONV, conv_transposed == 1 (data gradient): A = dL/dy [Bimg,Ho,Wo,Cin] (Cin = the conv's OUTPUT channels),
+     *     rows m = INPUT pixels (M = Bimg*H*W), tap (ky,kx) of row (b,hi,wi) reads dy[b, (hi+1-ky)/2, (wi+1-kx)/2] where both
+     *     numerators are even and in range, zero elsewhere - no zero-dilated copy of dy; B = the filter as [C][(ky,kx)][N]
+     *     (trid_weight_transpose_f32 WITHOUT flip: the taps are the forward ones).
+     *   b_mode TRID_B_CONV (weight gradient): B = x [Bimg,H,W,Cin], rows k = OUTPUT pixels (K = Bimg*Ho*Wo), the forward map. */
+    int32_t conv_stride;
+    int32_t conv_transposed;
 } trid_gemm_desc;
 
 int trid_gemm_f32(const trid_gemm_desc* d, void* stream);
@@ -223,6 +235,38 @@ int trid_weight_transpose_f32(const float* w, float* wt, int N, int T, int C, in
  * columns zero-filled). */
 int trid_stem_im2col_f32(const float* img, float* col, int B, int Cin, int H, int W, int Ho, int Wo,
                          int ldcol, void* stream);
+
+/* ---- the ImageNet ResNet-50/101 image encoder (csrc/resnet_ops.hip; reference lib/models/backbones/resnet.py).
+ * Its stem convolution nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False) (resnet.py:114,156) straight from the NCHW image
+ * batch [B][3][Hi][Wi] on the exact fp32 MFMA, K = 147 padded inside the kernel, no im2col tensor: y [B][Ho][Wo][64] with
+ * Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1; w [64][3][7][7] as stored; stats (may be NULL): [ceil(M/128)][64][2] =
+ * per-128-row (mean, M2) BatchNorm partials (trid_bn_finalize_f32 with rows_per_part 128). */
+int trid_stem7_conv_f32(const float* img, const float* w, float* y, float* stats, int B, int Hi, int Wi, void* stream);
+/* its weight gradient (autograd of resnet.py:114,156; the image needs no gradient): dw [64][3][7][7] (parameter layout) from the
+ * image batch and dy [B][Ho][Wo][64], the image gathered the same way; slabs: trid_stem7_conv_wgrad_slabs() x 64 * 147 floats of
+ * scratch, one slab per workgroup, folded in a fixed order (trid_slab_reduce_f32). */
+int trid_stem7_conv_wgrad_slabs(void);
+int trid_stem7_conv_wgrad_f32(const float* img, const float* dy, float* dw, float* slabs, int B, int Hi, int Wi, void* stream);
+/* bn1 + ReLU + nn.MaxPool2d(kernel_size=3, stride=2, padding=1) in one pass (resnet.py:115-117,157-159):
+ * out[b][hp][wp][c] = max over the window of relu(scale[c] * y + shift[c]), y [B][H][W][C] (C % 4 == 0), out [B][Hp][Wp][C] with
+ * Hp = (H - 1) / 2 + 1, Wp = (W - 1) / 2 + 1; padding never wins.  amax: as trid_bn_apply_f32. */
+int trid_bn_relu_maxpool_f32(const float* y, const float* scale, const float* shift, float* out, int B, int H, int W, int C,
+                             float* amax, void* stream);
+/* the pool's backward (autograd of resnet.py:117,159) as a gather: dx [B][H][W][C] = the gradient with respect to the ReLU
+ * OUTPUT, g [B][Hp][Wp][C].  Every input position recomputes the winner of the at most four windows that contain it from y,
+ * scale and shift (first maximum in row-major window order, PyTorch's rule) and sums the matching g: no atomics, no index
+ * tensor.  trid_bn_bwd_* with mask_mode 1 takes dx next (a window that is all <= 0 ties at zero: the ReLU mask removes it). */
+int trid_bn_relu_maxpool_bwd_f32(const float* g, const float* y, const float* scale, const float* shift, float* dx, int B, int H, int W,
+                                 int C, void* stream);
+/* The input of a stride-2 1x1 convolution (the downsample branch nn.Conv2d(inplanes, planes * 4, 1, stride=stride), resnet.py:137-143):
+ * out[b][ho][wo][c] = x[b][2 ho][2 wo][c], out [B][(H-1)/2+1][(W-1)/2+1][C]; amax as above.  Backward: dx [B][H][W][C] = g at the
+ * even positions, zero elsewhere (conv1's data gradient then accumulates onto it). */
+int trid_subsample2_f32(const float* x, float* out, int B, int H, int W, int C, float* amax, void* stream);
+int trid_subsample2_bwd_f32(const float* g, float* dx, int B, int H, int W, int C, void* stream);
+/* nn.AdaptiveAvgPool2d((1, 1)) (resnet.py:130,165): out [B][C] = mean over the HW pixels of x [B][HW][C], summed in pixel order;
+ * backward: dx [B][HW][C] = g[b][c] / HW. */
+int trid_global_avgpool_f32(const float* x, float* out, int B, int HW, int C, void* stream);
+int trid_global_avgpool_bwd_f32(const float* g, float* dx, int B, int HW, int C, void* stream);
 
 /* ---- the stem as bandwidth-shaped kernels (csrc/stem_conv.hip): every input pixel crosses the load path once.
  * Stem conv1 (nn.Conv2d(3, 32, 3, stride=2, padding=1, bias=False), m_resnet.py:161,205) straight from the NCHW image

@@ -3,8 +3,10 @@
 registered; any other name raises ``NotImplementedError`` as the reference does."""
 from .gru import build_gru
 from .m_resnet import build_m_resnet
+from .resnet import build_resnet
 
 _VISUAL = dict.fromkeys(("m_resnet", "m_resnet50", "m_resnet101"), build_m_resnet)
+_VISUAL.update(dict.fromkeys(("resnet50", "resnet101"), build_resnet))
 _TEXTUAL = {"bigru": lambda cfg, vocab_dict: build_gru(cfg, bidirectional=True, vocab_dict=vocab_dict)}
 
 
@@ -12,7 +14,7 @@ def _lookup(table, name):
     try:
         return table[name]
     except KeyError:
-        # torchvision-style resnet50/101 and the BERT text encoder are outside the path
+        # the BasicBlock ResNets (resnet18/34), resnet152 and the BERT / LSTM text encoders are outside the path
         raise NotImplementedError(name) from None
 
 

@@ -151,3 +151,24 @@ def baseline_cfg(visual="m_resnet50", height=384, width=128, num_classes=11003):
     cfg = moco_cfg(visual, height=height, width=width, num_classes=num_classes)
     cfg.MODEL.EMBEDDING.EMBED_HEAD = "simple"
     return cfg
+
+
+def imagenet_cfg(visual="resnet50", height=384, width=128, num_classes=11003):
+    """The shipped ``baseline_gru_rn50_ls_bs128.yaml`` settings: the ImageNet ResNet (``backbones/resnet.py``) and the
+    ``nn.Embedding`` form of the BiGRU (12000-word vocabulary) under ``EMBED_HEAD: 'simple'``."""
+    cfg = get_cfg_defaults()
+    cfg.MODEL.VISUAL_MODEL = visual
+    cfg.MODEL.TEXTUAL_MODEL = "bigru"
+    cfg.MODEL.NUM_CLASSES = num_classes
+    cfg.MODEL.GRU.ONEHOT = "yes"
+    cfg.MODEL.GRU.VOCABULARY_SIZE = 12000
+    cfg.MODEL.GRU.DROPOUT_KEEP_PROB = 1.0
+    cfg.MODEL.RESNET.RES5_STRIDE = 1
+    cfg.MODEL.EMBEDDING.EMBED_HEAD = "simple"
+    cfg.MODEL.EMBEDDING.FEATURE_SIZE = 256
+    cfg.MODEL.EMBEDDING.DROPOUT_PROB = 0.0
+    cfg.MODEL.EMBEDDING.EPSILON = 0.1
+    cfg.INPUT.HEIGHT, cfg.INPUT.WIDTH = height, width
+    cfg.SOLVER.IMS_PER_BATCH = 128
+    cfg.SOLVER.BASE_LR = 0.0001
+    return cfg

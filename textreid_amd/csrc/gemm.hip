@@ -7,6 +7,9 @@
 //   A_KC   A[m*lda + k]            rows K-contiguous       (activations, NT / NN)
 //   A_MC   A[k*lda + m]            rows M-contiguous       (dY in weight-gradient, TN)
 //   A_CONV NHWC image gather, k=(tap,c), 3x3 stride 1 pad 1 (implicit-GEMM fwd / dgrad)
+//          CS = 1 / 2: the stride-2 forward / transposed (data-gradient) gather of resnet.py:62-70 - still a per-row
+//          base + per-tap offset + per-row tap validity, chosen at launch time (template parameter): the stride-1
+//          instantiations (CS = 0) are the kernels as they were
 //   B_KC   B[n*ldb + k]            weights [N,K]            (NT)
 //   B_NC   B[k*ldb + n]            rows N-contiguous        (NN / TN)
 //   B_CONV NHWC image gather on rows k=pixel, n=(tap,c)     (implicit-GEMM wgrad)
@@ -30,7 +33,7 @@
 namespace trid {
 
 
-template <int AMODE, int BMODE, int BM, int BN, int WAVES_M, int WAVES_N>
+template <int AMODE, int BMODE, int BM, int BN, int WAVES_M, int WAVES_N, int CS = 0>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_kernel(GemmParams p) {
     constexpr int NTHREADS = WAVES_M * WAVES_N * 64;
     static_assert(NTHREADS == 256 || NTHREADS == 512, "4 or 8 waves per workgroup");
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_kernel(GemmParams
 
     // A_CONV: per-row pixel coordinates
     int a_y[NA], a_x[NA];
-    if (AMODE == A_CONV) {
+    long long a_pix[NA];  // CS != 0: source pixel the taps are relative to (CS 1: (b, 2y, 2x); CS 2: (b, 0, 0))
+    if (AMODE == A_CONV && CS == 0) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             int m = m0 + a_r + i * A_RPP;
@@ -87,6 +91,25 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_kernel(GemmParams
             a_x[i] = m - (int)q * p.W;
             uint32_t b = fdiv(q, p.fdH);
             a_y[i] = (int)q - (int)b * p.H;
+        }
+    }
+    if (AMODE == A_CONV && CS != 0) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int m = m0 + a_r + i * A_RPP;
+            const uint32_t q = fdiv((uint32_t)m, p.fdW);
+            const int x = m - (int)q * p.RW;
+            const uint32_t b = fdiv(q, p.fdH);
+            const int y = (int)q - (int)b * p.RH;
+            if (CS == 1) {
+                a_y[i] = 2 * y;
+                a_x[i] = 2 * x;
+                a_pix[i] = ((long long)b * p.SH + 2 * y) * p.SW + 2 * x;
+            } else {
+                a_y[i] = y + 1;
+                a_x[i] = x + 1;
+                a_pix[i] = (long long)b * p.SH * p.SW;
+            }
         }
     }
     // B_CONV: per-thread fixed column quad -> (tap, c)
@@ -123,11 +146,25 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_kernel(GemmParams
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
                 const int m = m0 + a_r + i * A_RPP;
-                const int yy = a_y[i] + dy, xx = a_x[i] + dx;
-                if (m < p.M && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W)
-                    ra[i] = *reinterpret_cast<const float4*>(A + (long long)(m + dy * p.W + dx) * p.Cin + c);
-                else
-                    ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (CS == 0) {
+                    const int yy = a_y[i] + dy, xx = a_x[i] + dx;
+                    if (m < p.M && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W)
+                        ra[i] = *reinterpret_cast<const float4*>(A + (long long)(m + dy * p.W + dx) * p.Cin + c);
+                    else
+                        ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                } else if (CS == 1) {
+                    const int yy = a_y[i] + dy, xx = a_x[i] + dx;
+                    if (m < p.M && k < k_end && yy >= 0 && yy < p.SH && xx >= 0 && xx < p.SW)
+                        ra[i] = *reinterpret_cast<const float4*>(A + (a_pix[i] + dy * p.SW + dx) * p.Cin + c);
+                    else
+                        ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {
+                    const int ty = a_y[i] - (dy + 1), tx = a_x[i] - (dx + 1);  // 2 ho, 2 wo where the tap exists
+                    if (m < p.M && k < k_end && ty >= 0 && tx >= 0 && ((ty | tx) & 1) == 0 && (ty >> 1) < p.SH && (tx >> 1) < p.SW)
+                        ra[i] = *reinterpret_cast<const float4*>(A + (a_pix[i] + (long long)(ty >> 1) * p.SW + (tx >> 1)) * p.Cin + c);
+                    else
+                        ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
         } else {  // A_MC
             const int m = m0 + 4 * a_q;
@@ -166,14 +203,25 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_kernel(GemmParams
             for (int i = 0; i < NB; ++i) {
                 const int k = k0 + b_r + i * B_RPP;
                 uint32_t q = fdiv((uint32_t)k, p.fdW);
-                const int x = k - (int)q * p.W;
-                uint32_t b = fdiv(q, p.fdH);
-                const int y = (int)q - (int)b * p.H;
-                const int yy = y + b_dy, xx = x + b_dx;
-                if (b_colok && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W)
-                    rb[i] = *reinterpret_cast<const float4*>(Bp + (long long)(k + b_dy * p.W + b_dx) * p.Cin + b_c);
-                else
-                    rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (CS == 0) {
+                    const int x = k - (int)q * p.W;
+                    uint32_t b = fdiv(q, p.fdH);
+                    const int y = (int)q - (int)b * p.H;
+                    const int yy = y + b_dy, xx = x + b_dx;
+                    if (b_colok && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W)
+                        rb[i] = *reinterpret_cast<const float4*>(Bp + (long long)(k + b_dy * p.W + b_dx) * p.Cin + b_c);
+                    else
+                        rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {  // rows are OUTPUT pixels of the stride-2 convolution
+                    const int x = k - (int)q * p.RW;
+                    const uint32_t b = fdiv(q, p.fdH);
+                    const int y = (int)q - (int)b * p.RH;
+                    const int yy = 2 * y + b_dy, xx = 2 * x + b_dx;
+                    if (b_colok && k < k_end && yy >= 0 && yy < p.SH && xx >= 0 && xx < p.SW)
+                        rb[i] = *reinterpret_cast<const float4*>(Bp + (((long long)b * p.SH + yy) * p.SW + xx) * p.Cin + b_c);
+                    else
+                        rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
         }
     };
@@ -404,7 +452,7 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
     }
 }
 
-template <int AMODE, int BMODE, int BM, int BN, int WAVES_M, int WAVES_N>
+template <int AMODE, int BMODE, int BM, int BN, int WAVES_M, int WAVES_N, int CS = 0>
 static int launch(GemmParams& p, hipStream_t stream) {
     p.mblocks = (p.M + BM - 1) / BM;
     p.nblocks = (p.N + BN - 1) / BN;
@@ -417,18 +465,18 @@ static int launch(GemmParams& p, hipStream_t stream) {
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
         if (lds > 48 * 1024)
-            attr_err = hipFuncSetAttribute((const void*)gemm_kernel<AMODE, BMODE, BM, BN, WAVES_M, WAVES_N>,
+            attr_err = hipFuncSetAttribute((const void*)gemm_kernel<AMODE, BMODE, BM, BN, WAVES_M, WAVES_N, CS>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
     if (attr_err != hipSuccess) {
         set_error("trid_gemm_f32: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(attr_err));
         return (int)attr_err;
     }
-    hipLaunchKernelGGL((gemm_kernel<AMODE, BMODE, BM, BN, WAVES_M, WAVES_N>), grid, dim3(WAVES_M * WAVES_N * 64), lds, stream, p);
+    hipLaunchKernelGGL((gemm_kernel<AMODE, BMODE, BM, BN, WAVES_M, WAVES_N, CS>), grid, dim3(WAVES_M * WAVES_N * 64), lds, stream, p);
     return check_launch("trid_gemm_f32");
 }
 
-template <int AMODE, int BMODE>
+template <int AMODE, int BMODE, int CS = 0>
 static int dispatch_tile(GemmParams& p, hipStream_t stream) {
     // tile choice: fill 128-wide tiles when the dimension allows, shrink otherwise.
     // The BatchNorm-statistics epilogue always runs on 128-row tiles so that the
@@ -439,17 +487,17 @@ static int dispatch_tile(GemmParams& p, hipStream_t stream) {
     if (bm == 128) {
         if (bn == 128) {
             static const bool four = getenv("TRID_GEMM4") != nullptr;  // A/B switch: 4-wave 64x64 wave tiles
-            if (!four) return launch<AMODE, BMODE, 128, 128, 2, 4>(p, stream);
-            return launch<AMODE, BMODE, 128, 128, 2, 2>(p, stream);
+            if (!four) return launch<AMODE, BMODE, 128, 128, 2, 4, CS>(p, stream);
+            return launch<AMODE, BMODE, 128, 128, 2, 2, CS>(p, stream);
         }
-        if (bn == 64) return launch<AMODE, BMODE, 128, 64, 2, 2>(p, stream);
-        return launch<AMODE, BMODE, 128, 32, 4, 1>(p, stream);
+        if (bn == 64) return launch<AMODE, BMODE, 128, 64, 2, 2, CS>(p, stream);
+        return launch<AMODE, BMODE, 128, 32, 4, 1, CS>(p, stream);
     }
     if (bn == 128) {
-        if (bm == 64) return launch<AMODE, BMODE, 64, 128, 2, 2>(p, stream);
-        return launch<AMODE, BMODE, 32, 128, 1, 4>(p, stream);
+        if (bm == 64) return launch<AMODE, BMODE, 64, 128, 2, 2, CS>(p, stream);
+        return launch<AMODE, BMODE, 32, 128, 1, 4, CS>(p, stream);
     }
-    return launch<AMODE, BMODE, 64, 64, 2, 2>(p, stream);  // small x small, masked
+    return launch<AMODE, BMODE, 64, 64, 2, 2, CS>(p, stream);  // small x small, masked
 }
 
 }  // namespace trid
@@ -477,6 +525,10 @@ int trid_gemm_launch(const trid_gemm_desc* d, const GemmFilter* filt, const int*
     p.bias = d->bias; p.sBias = d->strideBias; p.stats = d->stats;
     p.res = d->residual; p.ldres = d->ldres; p.relu = d->relu;
     p.H = d->H; p.W = d->W; p.Cin = d->Cin;
+    TRID_REQUIRE(d->conv_stride >= 0 && d->conv_stride <= 2 && (d->conv_transposed == 0 || d->conv_transposed == 1), "trid_gemm_f32: conv_stride must be 0, 1 or 2");
+    // 0: the stride-1 gathers; 1: stride-2 forward map (A_CONV forward, B_CONV weight gradient); 2: stride-2 transposed map (data gradient)
+    const int cs = (d->conv_stride == 2 && (d->a_mode == A_CONV || d->b_mode == B_CONV)) ? (d->conv_transposed ? 2 : 1) : 0;
+    TRID_REQUIRE(cs != 0 || d->conv_transposed == 0, "trid_gemm_f32: conv_transposed needs conv_stride == 2 and a_mode A_CONV");
     if (filt) p.filt = *filt;
     p.gate = gate;
     // contiguous-direction alignment (float4 loads)
@@ -486,10 +538,22 @@ int trid_gemm_launch(const trid_gemm_desc* d, const GemmFilter* filt, const int*
     if (d->b_mode == B_NC) TRID_REQUIRE(d->N % 4 == 0 && d->ldb % 4 == 0, "B_NC needs N%%4==0 and ldb%%4==0 (N=%d)", d->N);
     if (d->a_mode == A_CONV || d->b_mode == B_CONV) {
         TRID_REQUIRE(d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cin % 4 == 0, "conv gather needs H,W>0 and Cin%%4==0");
-        if (d->a_mode == A_CONV) TRID_REQUIRE(d->K == 9 * d->Cin && d->M % (d->H * d->W) == 0, "A_CONV: K must be 9*Cin and M a multiple of H*W");
-        if (d->b_mode == B_CONV) TRID_REQUIRE(d->N == 9 * d->Cin && d->K % (d->H * d->W) == 0, "B_CONV: N must be 9*Cin and K a multiple of H*W");
-        p.fdW = make_fastdiv((uint32_t)d->W);
-        p.fdH = make_fastdiv((uint32_t)d->H);
+        if (cs == 0) {
+            if (d->a_mode == A_CONV) TRID_REQUIRE(d->K == 9 * d->Cin && d->M % (d->H * d->W) == 0, "A_CONV: K must be 9*Cin and M a multiple of H*W");
+            if (d->b_mode == B_CONV) TRID_REQUIRE(d->N == 9 * d->Cin && d->K % (d->H * d->W) == 0, "B_CONV: N must be 9*Cin and K a multiple of H*W");
+            p.fdW = make_fastdiv((uint32_t)d->W);
+            p.fdH = make_fastdiv((uint32_t)d->H);
+        } else {
+            const int Ho = (d->H - 1) / 2 + 1, Wo = (d->W - 1) / 2 + 1;
+            TRID_REQUIRE(!(d->a_mode == A_CONV && d->b_mode == B_CONV), "stride-2 gather: one conv operand per product");
+            TRID_REQUIRE(d->b_mode != B_CONV || cs == 1, "B_CONV (weight gradient) takes the forward map: conv_transposed must be 0");
+            if (cs == 1) { p.RH = Ho; p.RW = Wo; p.SH = d->H; p.SW = d->W; }
+            else         { p.RH = d->H; p.RW = d->W; p.SH = Ho; p.SW = Wo; }
+            if (d->a_mode == A_CONV) TRID_REQUIRE(d->K == 9 * d->Cin && d->M % (p.RH * p.RW) == 0, "A_CONV (stride 2): K must be 9*Cin and M a multiple of the row map (%d x %d)", p.RH, p.RW);
+            if (d->b_mode == B_CONV) TRID_REQUIRE(d->N == 9 * d->Cin && d->K % (Ho * Wo) == 0, "B_CONV (stride 2): N must be 9*Cin and K a multiple of Ho*Wo");
+            p.fdW = make_fastdiv((uint32_t)p.RW);
+            p.fdH = make_fastdiv((uint32_t)p.RH);
+        }
         p.fdC = make_fastdiv((uint32_t)d->Cin);
     }
     TRID_REQUIRE(!(d->stats && (d->splits != 1 || d->batch != 1)), "stats epilogue needs splits==1, batch==1");
@@ -503,8 +567,10 @@ int trid_gemm_launch(const trid_gemm_desc* d, const GemmFilter* filt, const int*
     int rc;
     const int am = d->a_mode, bm = d->b_mode;
     // the split kernels address operands with 31-bit byte offsets (buffer loads): < 2 GB per operand and batch
+    // (stride-2 A_CONV: the source map of the row map's images, plus the margin the shifted descriptor base and rows beyond M need)
+    const long long a_src = (am == A_CONV && cs != 0) ? ((long long)d->M / (p.RH * p.RW) + 1) * p.SH * p.SW : d->M;
     const long long a_elems = am == A_KC ? (long long)(d->M + 256) * d->lda
-                            : am == A_MC ? (long long)d->K * d->lda : (long long)(d->M + 256 + 2 * d->W + 2) * d->Cin;
+                            : am == A_MC ? (long long)d->K * d->lda : (long long)(a_src + 256 + 2 * d->W + 2) * d->Cin;
     const long long b_elems = bm == B_KC ? (long long)(d->N + 128) * d->ldb : bm == B_NC ? (long long)d->K * d->ldb : 0;
     const bool small_enough = a_elems < (1ll << 29) && b_elems < (1ll << 29);
     p.a_amax = d->a_amax;
@@ -514,10 +580,16 @@ int trid_gemm_launch(const trid_gemm_desc* d, const GemmFilter* filt, const int*
     const int min_n = d->precision == 16 ? 32 : 64;
     if ((d->precision == 1 || d->precision == 3 || d->precision == 6 || d->precision == 16) && d->K % 8 == 0 && d->K >= 32 && d->M >= 64 && d->N >= min_n &&
         (d->M >= 96 || d->N >= 96) && (am != A_CONV || d->Cin % 8 == 0) && small_enough) {
-        rc = gemm_bf16_dispatch(p, am, bm, d->precision, stream);
+        rc = gemm_bf16_dispatch(p, am, bm, d->precision, cs, stream);
         if (rc != TRID_E_UNSUPPORTED) return rc;
     }
     if (filt) return TRID_E_UNSUPPORTED;  // the filter epilogue exists in the split kernel only
+    if (cs != 0) {
+        if (am == A_CONV && bm == B_KC) return cs == 1 ? dispatch_tile<A_CONV, B_KC, 1>(p, stream) : dispatch_tile<A_CONV, B_KC, 2>(p, stream);
+        if (am == A_MC && bm == B_CONV) return dispatch_tile<A_MC, B_CONV, 1>(p, stream);
+        set_error("trid_gemm_f32: unsupported loader combination a=%d b=%d for a stride-2 gather", am, bm);
+        return TRID_E_UNSUPPORTED;
+    }
     if (am == A_KC && bm == B_KC) rc = dispatch_tile<A_KC, B_KC>(p, stream);
     else if (am == A_CONV && bm == B_KC) rc = dispatch_tile<A_CONV, B_KC>(p, stream);
     else if (am == A_KC && bm == B_NC) rc = dispatch_tile<A_KC, B_NC>(p, stream);

@@ -44,7 +44,9 @@ __host__ __device__ constexpr int b_plane_slots(int bmode, int bn) { return (bmo
 __host__ __device__ constexpr int tile_rows(int bn) { return bn == 32 ? 256 : BM_T; }
 
 // ARITH: 1 / 2 / 3 = number of bf16 planes (1, 3, 6 products); 16 = two fp16 planes, 3 products, one accumulator
-template <int AMODE, int BMODE, int ARITH, int BN>
+// CS: 0 = the stride-1 3x3 gathers; 1 / 2 = the stride-2 forward / transposed gathers (GemmParams RH..SW; resnet.py:62-70 and its
+// autograd).  Only the per-row setup (base offset, tap mask) and the per-tile scalar offset differ: the K loop is the same
+template <int AMODE, int BMODE, int ARITH, int BN, int CS = 0>
 __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES > 0 && ARITH != 16) ? TRID_NARROW_WAVES : (ARITH == 16 ? ((BMODE == B_KC && AMODE != A_MC && BN != 32) ? TRID_F16_WAVES_KC : TRID_F16_WAVES) : 1)) void gemm_bf16s_kernel(GemmParams p) {
     constexpr bool F16 = (ARITH == 16);
     constexpr int NPL = F16 ? 2 : ARITH;
@@ -111,21 +113,54 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
     const bool permute = (AMODE == A_CONV) && (BMODE == B_KC) && (p.Cin % BK == 0) && p.splits == 1;
 
     const long long a_ld = (AMODE == A_CONV) ? p.Cin : p.lda;
-    const long long a_rows = (AMODE == A_KC) ? p.M : (AMODE == A_MC) ? p.K : (long long)p.M + 2 * p.W + 2;
-    const float* a_base = (AMODE == A_CONV) ? A - (long long)(p.W + 1) * p.Cin : A;  // tap offsets stay >= 0
+    const int srcW = (CS != 0) ? p.SW : p.W;  // width of the gathered map
+    const long long a_rows = (AMODE == A_KC) ? p.M : (AMODE == A_MC) ? p.K
+                             : (CS != 0 ? (long long)(p.M / (p.RH * p.RW)) * p.SH * p.SW : (long long)p.M) + 2 * srcW + 2;
+    const float* a_base = (AMODE == A_CONV) ? A - (long long)(srcW + 1) * p.Cin : A;  // tap offsets stay >= 0
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, (unsigned)(a_rows * a_ld * 4), 0x00020000);
     const long long b_rows = (BMODE == B_KC) ? p.N : p.K;
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, 0, (unsigned)(b_rows * p.ldb * 4), 0x00020000);
 
     constexpr int APASS = BM / 128;  // a loader pass covers 128 A rows
     int a_y[APASS], a_x[APASS];
+    long long a_pix[APASS];  // CS != 0, general gather: the source pixel the taps are relative to
     unsigned voA[APASS], amask[APASS];
 #pragma unroll
     for (int ps = 0; ps < APASS; ++ps) {
         const int m = m0 + a_row + ps * 128;
         voA[ps] = (unsigned)(((long long)m * a_ld + 8 * a_kg) * 4);
         amask[ps] = 0x1ffu;
-        if (AMODE == A_CONV) {
+        if (AMODE == A_CONV && CS != 0) {
+            const uint32_t q = fdiv((uint32_t)m, p.fdW);
+            const int x = m - (int)q * p.RW;
+            const uint32_t b = fdiv(q, p.fdH);
+            const int y = (int)q - (int)b * p.RH;
+            unsigned mk = 0;
+            long long pix;  // row base: pixel of the source map that tap offset 0 of the shifted descriptor refers to
+            if (CS == 1) {
+                a_y[ps] = 2 * y; a_x[ps] = 2 * x;
+                pix = ((long long)b * p.SH + 2 * y) * p.SW + 2 * x;
+                a_pix[ps] = pix;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int yy = 2 * y + t / 3 - 1, xx = 2 * x + t % 3 - 1;
+                    if (yy >= 0 && yy < p.SH && xx >= 0 && xx < p.SW) mk |= 1u << t;
+                }
+            } else {
+                a_y[ps] = y + 1; a_x[ps] = x + 1;
+                pix = ((long long)b * p.SH + (y + 1) / 2) * p.SW + (x + 1) / 2;
+                a_pix[ps] = (long long)b * p.SH * p.SW;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int ty = y + 1 - t / 3, tx = x + 1 - t % 3;
+                    if (ty >= 0 && tx >= 0 && ((ty | tx) & 1) == 0 && (ty >> 1) < p.SH && (tx >> 1) < p.SW) mk |= 1u << t;
+                }
+            }
+            const bool live = m < p.M;
+            voA[ps] = live ? (unsigned)((pix * a_ld + 8 * a_kg) * 4) : 0u;
+            amask[ps] = live ? mk : 0u;
+        }
+        if (AMODE == A_CONV && CS == 0) {
             const uint32_t q = fdiv((uint32_t)m, p.fdW);
             a_x[ps] = m - (int)q * p.W;
             const uint32_t b = fdiv(q, p.fdH);
@@ -167,7 +202,8 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
             int tap = 0;
             if (AMODE == A_CONV) {
                 tap = k0 / p.Cin;  // uniform: a tile never straddles taps when Cin % BK == 0
-                so = (unsigned)((((tap / 3) * p.W + (tap % 3)) * p.Cin + (k0 - tap * p.Cin)) * 4);
+                if (CS == 2) so = (unsigned)((((1 - (tap / 3) / 2) * srcW + (1 - (tap % 3) / 2)) * p.Cin + (k0 - tap * p.Cin)) * 4);
+                else so = (unsigned)((((tap / 3) * srcW + (tap % 3)) * p.Cin + (k0 - tap * p.Cin)) * 4);
             } else {
                 so = (unsigned)(k0 * 4);
                 kill = (k0 + 8 * a_kg < k_end) ? 0u : OOB;
@@ -188,9 +224,21 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
                 const uint32_t tap = fdiv((uint32_t)k, p.fdC);
                 const int c = k - (int)tap * p.Cin;
                 const int dy = (int)tap / 3 - 1, dx = (int)tap % 3 - 1;
-                const int yy = a_y[ps] + dy, xx = a_x[ps] + dx;
-                const bool ok = m < p.M && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-                const float* src = A + (long long)(m + dy * p.W + dx) * p.Cin + c;
+                bool ok;
+                const float* src;
+                if (CS == 0) {
+                    const int yy = a_y[ps] + dy, xx = a_x[ps] + dx;
+                    ok = m < p.M && k < k_end && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
+                    src = A + (long long)(m + dy * p.W + dx) * p.Cin + c;
+                } else if (CS == 1) {
+                    const int yy = a_y[ps] + dy, xx = a_x[ps] + dx;
+                    ok = m < p.M && k < k_end && yy >= 0 && yy < p.SH && xx >= 0 && xx < p.SW;
+                    src = A + (a_pix[ps] + dy * p.SW + dx) * p.Cin + c;
+                } else {
+                    const int ty = a_y[ps] - (dy + 1), tx = a_x[ps] - (dx + 1);
+                    ok = m < p.M && k < k_end && ty >= 0 && tx >= 0 && ((ty | tx) & 1) == 0 && (ty >> 1) < p.SH && (tx >> 1) < p.SW;
+                    src = A + (a_pix[ps] + (long long)(ty >> 1) * p.SW + (tx >> 1)) * p.Cin + c;
+                }
                 const float4 u = ld4_if(ok, src, A), v = ld4_if(ok, src + 4, A);
                 ra[ps][0] = u.x; ra[ps][1] = u.y; ra[ps][2] = u.z; ra[ps][3] = u.w;
                 ra[ps][4] = v.x; ra[ps][5] = v.y; ra[ps][6] = v.z; ra[ps][7] = v.w;
@@ -215,7 +263,19 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
             if (b_wide_lane) {
                 const int n = n0 + 4 * w_mq;
                 const int kbase = k0 + 4 * w_kq;  // multiple of 4
-                if ((p.W & 3) == 0) {
+                if (CS != 0) {  // rows are OUTPUT pixels of the stride-2 convolution (map RH x RW), the image is the input map
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = kbase + j;
+                        const uint32_t q = fdiv((uint32_t)k, p.fdW);
+                        const int x = k - (int)q * p.RW;
+                        const uint32_t b = fdiv(q, p.fdH);
+                        const int y = (int)q - (int)b * p.RH;
+                        const int yy = 2 * y + b_dy, xx = 2 * x + b_dx;
+                        wb[j] = ld4_if(4 * w_mq < BN && n < p.N && k < k_end && yy >= 0 && yy < p.SH && xx >= 0 && xx < p.SW,
+                                       Bp + (((long long)b * p.SH + yy) * p.SW + xx) * p.Cin + b_c, Bp);
+                    }
+                } else if ((p.W & 3) == 0) {
                     // 4 consecutive pixels stay in one image row when W % 4 == 0: one decomposition
                     const uint32_t q = fdiv((uint32_t)kbase, p.fdW);
                     const int x0 = kbase - (int)q * p.W;
@@ -460,7 +520,7 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
     }
 }
 
-template <int AMODE, int BMODE, int ARITH, int BN>
+template <int AMODE, int BMODE, int ARITH, int BN, int CS = 0>
 static int launch_bf16(GemmParams& p, hipStream_t stream) {
     constexpr int NPL = ARITH == 16 ? 2 : ARITH;
     p.mblocks = (p.M + tile_rows(BN) - 1) / tile_rows(BN);
@@ -472,31 +532,36 @@ static int launch_bf16(GemmParams& p, hipStream_t stream) {
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
         if (lds > 48 * 1024)
-            attr_err = hipFuncSetAttribute((const void*)gemm_bf16s_kernel<AMODE, BMODE, ARITH, BN>,
+            attr_err = hipFuncSetAttribute((const void*)gemm_bf16s_kernel<AMODE, BMODE, ARITH, BN, CS>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
     if (attr_err != hipSuccess) {
         set_error("trid_gemm_f32(split): cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(attr_err));
         return (int)attr_err;
     }
-    hipLaunchKernelGGL((gemm_bf16s_kernel<AMODE, BMODE, ARITH, BN>), grid, dim3(NT), lds, stream, p);
+    hipLaunchKernelGGL((gemm_bf16s_kernel<AMODE, BMODE, ARITH, BN, CS>), grid, dim3(NT), lds, stream, p);
     return check_launch("trid_gemm_f32(split)");
 }
 
-template <int AMODE, int BMODE, int NPL>
+template <int AMODE, int BMODE, int NPL, int CS = 0>
 static int pick_tile(GemmParams& p, hipStream_t stream) {
     // 128-row tiles, two workgroups per CU; 64 columns when the output is that narrow.  (A 256x128
     // double-buffered tile with one workgroup per CU and a role-alternating 256x128 schedule were both
     // measured 3-4 % slower on the same box)
     if constexpr (NPL == 16 && BMODE == B_KC && AMODE != A_MC) {
-        if (p.N <= 32) return launch_bf16<AMODE, BMODE, NPL, 32>(p, stream);  // stem convolutions
+        if (p.N <= 32) return launch_bf16<AMODE, BMODE, NPL, 32, CS>(p, stream);  // stem convolutions
     }
-    if (p.N <= 64) return launch_bf16<AMODE, BMODE, NPL, 64>(p, stream);
-    return launch_bf16<AMODE, BMODE, NPL, 128>(p, stream);
+    if (p.N <= 64) return launch_bf16<AMODE, BMODE, NPL, 64, CS>(p, stream);
+    return launch_bf16<AMODE, BMODE, NPL, 128, CS>(p, stream);
 }
 
 template <int NPL>
-static int dispatch_modes(GemmParams& p, int am, int bm, hipStream_t stream) {
+static int dispatch_modes(GemmParams& p, int am, int bm, int cs, hipStream_t stream) {
+    if (cs != 0) {  // the stride-2 gathers: forward / data gradient (A_CONV) and weight gradient (B_CONV)
+        if (am == A_CONV && bm == B_KC) return cs == 1 ? pick_tile<A_CONV, B_KC, NPL, 1>(p, stream) : pick_tile<A_CONV, B_KC, NPL, 2>(p, stream);
+        if (am == A_MC && bm == B_CONV && cs == 1) return pick_tile<A_MC, B_CONV, NPL, 1>(p, stream);
+        return TRID_E_UNSUPPORTED;
+    }
     if (am == A_KC && bm == B_KC) return pick_tile<A_KC, B_KC, NPL>(p, stream);
     if (am == A_CONV && bm == B_KC) return pick_tile<A_CONV, B_KC, NPL>(p, stream);
     if (am == A_KC && bm == B_NC) return pick_tile<A_KC, B_NC, NPL>(p, stream);
@@ -505,11 +570,11 @@ static int dispatch_modes(GemmParams& p, int am, int bm, hipStream_t stream) {
     return TRID_E_UNSUPPORTED;
 }
 
-int gemm_bf16_dispatch(GemmParams& p, int a_mode, int b_mode, int precision, hipStream_t stream) {
-    if (precision == 16) return dispatch_modes<16>(p, a_mode, b_mode, stream);
-    if (precision == 6) return dispatch_modes<3>(p, a_mode, b_mode, stream);
-    if (precision == 1) return dispatch_modes<1>(p, a_mode, b_mode, stream);
-    return dispatch_modes<2>(p, a_mode, b_mode, stream);
+int gemm_bf16_dispatch(GemmParams& p, int a_mode, int b_mode, int precision, int cs, hipStream_t stream) {
+    if (precision == 16) return dispatch_modes<16>(p, a_mode, b_mode, cs, stream);
+    if (precision == 6) return dispatch_modes<3>(p, a_mode, b_mode, cs, stream);
+    if (precision == 1) return dispatch_modes<1>(p, a_mode, b_mode, cs, stream);
+    return dispatch_modes<2>(p, a_mode, b_mode, cs, stream);
 }
 
 }  // namespace trid

@@ -97,13 +97,18 @@ struct GemmParams {
     EvalBound ev;
     int pool_w;             // > 0: the epilogue output is the 2x2 average pool of act(.) over images of this width ([M / 4][N])
     BnBwdFuse bb;
+    // stride-2 3x3 gathers (gemm.hip / gemm_bf16.hip, template parameter CS; all zero for the stride-1 kernels).  Rows (A_CONV: m,
+    // B_CONV: k) are pixels of the ROW map [RH][RW], the gathered tensor is the SOURCE map [SH][SW][Cin]; fdW / fdH divide by RW / RH.
+    //   CS 1 (forward, weight gradient): rows = output pixels, source = x;  tap (ky,kx) reads x[2y-1+ky][2x-1+kx]
+    //   CS 2 (data gradient):            rows = input pixels,  source = dy; tap (ky,kx) reads dy[(y+1-ky)/2][(x+1-kx)/2] where both are even
+    int RH, RW, SH, SW;
 };
 
 constexpr int BK = 32;
 
 // split-precision variants (gemm_bf16.hip): fp32 operands split on the fly into 2 or 3
 // bf16 planes, 3 or 6 bf16 MFMAs per product, fp32 accumulation
-int gemm_bf16_dispatch(GemmParams& p, int a_mode, int b_mode, int precision, hipStream_t stream);
+int gemm_bf16_dispatch(GemmParams& p, int a_mode, int b_mode, int precision, int cs, hipStream_t stream);
 
 }  // namespace trid
 

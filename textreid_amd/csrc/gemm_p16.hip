@@ -1462,6 +1462,7 @@ extern "C" int trid_gemm_p16_wgrad(const trid_gemm_desc* d, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     TRID_REQUIRE(d != nullptr && d->A && d->B && d->C, "trid_gemm_p16_wgrad: null operand");
     TRID_REQUIRE(d->a_mode == A_MC && (d->b_mode == B_NC || d->b_mode == B_CONV), "trid_gemm_p16_wgrad: loader modes A_MC x B_NC / B_CONV only");
+    TRID_REQUIRE(d->conv_stride != 2, "trid_gemm_p16_wgrad: the stride-2 gather is a trid_gemm_f32 loader");
     const int planes = d->precision == 1 ? 1 : 2;  // precision 1: plain bf16 operands; else P16
     const int gc = planes == 1 ? 64 : 32;
     TRID_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->M % gc == 0 && d->N % gc == 0 && d->lda % gc == 0,
@@ -1533,6 +1534,7 @@ extern "C" int trid_gemm_p16(const trid_gemm_desc* d, int variant, void* stream_
     const int bke = planes == 1 ? 64 : 32;
     TRID_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->K % bke == 0, "trid_gemm_p16: K must be a positive multiple of %d (K=%d)", bke, d->K);
     TRID_REQUIRE((d->a_mode == A_KC || d->a_mode == A_CONV) && d->b_mode == B_KC, "trid_gemm_p16: loader modes A_KC / A_CONV x B_KC only");
+    TRID_REQUIRE(d->conv_stride != 2, "trid_gemm_p16: the stride-2 gather is a trid_gemm_f32 loader");
     TRID_REQUIRE(aligned16(d->A) && aligned16(d->B) && aligned16(d->C), "trid_gemm_p16: operands must be 16-byte aligned");
     TRID_REQUIRE(d->batch >= 1 && d->splits >= 1, "trid_gemm_p16: batch/splits must be >= 1");
     TRID_REQUIRE(d->lda % 32 == 0 && d->ldb % 32 == 0, "trid_gemm_p16: row pitches must be multiples of 32 elements");

@@ -70,6 +70,8 @@ class GemmDesc(ctypes.Structure):
         ("bnb_ws2", ctypes.c_void_p),
         ("bnb_relu", ctypes.c_int32),
         ("bnb_mask", ctypes.c_void_p),
+        ("conv_stride", ctypes.c_int32),
+        ("conv_transposed", ctypes.c_int32),
     ]
 
 

@@ -169,10 +169,13 @@ def amax(t):
 
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_mode=A_KC, b_mode=B_KC, alpha=1.0, accumulate=False, bias=None,
          stats=None, batch=1, strideA=0, strideB=0, strideC=0, splits=1, strideSplit=0, conv=None, a_off=0, b_off=0,
-         c_off=0, strideBias=0, bias_off=0, residual=None, ldres=0, relu=False, precision=None, a_amax=None, b_amax=None):
+         c_off=0, strideBias=0, bias_off=0, residual=None, ldres=0, relu=False, precision=None, a_amax=None, b_amax=None,
+         conv_stride=1, conv_transposed=False):
     """Raw descriptor call.  a_off/b_off/c_off are element offsets into A/B/C.  precision=16 (fp16-split
     arithmetic) takes the operands' largest magnitudes as device scalars; a missing one is computed here over the
-    WHOLE tensor object passed (a superset of the operand is a valid, merely looser, scale)."""
+    WHOLE tensor object passed (a superset of the operand is a valid, merely looser, scale).
+    conv_stride=2 (with conv=(H, W, Cin) of the convolution's INPUT map): the stride-2 3x3 gathers, conv_transposed for
+    the data gradient (trid_gemm_desc.conv_stride)."""
     if (a_mode == A_KC and b_mode in (B_KC, B_NC) and stats is None and splits == 1 and residual is None and not relu and conv is None
             and a_off == 0 and b_off == 0 and c_off == 0 and bias_off == 0 and batch <= 65535
             and _skinny_ok(M, N, K, lda, ldb if b_mode == B_KC else None, precision, SKINNY_MIN_K_BATCHED) and A.data_ptr() % 16 == 0
@@ -202,6 +205,8 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_mode=A_KC, b_mode=B_KC, alpha=1.0, a
     d.stats = _p(stats)
     if conv is not None:
         d.H, d.W, d.Cin = conv
+        if conv_stride != 1:
+            d.conv_stride, d.conv_transposed = conv_stride, 1 if conv_transposed else 0
     d.precision = prec
     d.a_amax = _p(a_amax)
     d.b_amax = _p(b_amax)
@@ -921,16 +926,34 @@ def conv1x1(x, w, stats=False, bias=None, relu=False, residual=None, prec=None, 
     return (y, st) if stats else y
 
 
-def conv3x3(x, w, stats=False, bias=None, relu=False, prec=None, aa=None, ba=None):
-    """x [B,H,W,C] NHWC, w [N, 9*C] (tap-major, channel-minor = OHWI) -> y [B,H,W,N]."""
+def conv3x3(x, w, stats=False, bias=None, relu=False, prec=None, aa=None, ba=None, stride=1):
+    """x [B,H,W,C] NHWC, w [N, 9*C] (tap-major, channel-minor = OHWI) -> y [B,Ho,Wo,N]; pad 1, stride 1 or 2
+    (Ho = (H - 1) // stride + 1)."""
     Bi, H, W, C = x.shape
     N = w.shape[0]
-    M = Bi * H * W
-    y = empty((Bi, H, W, N), x)
+    if stride not in (1, 2):
+        raise ValueError("conv3x3: stride must be 1 or 2")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    M = Bi * Ho * Wo
+    y = empty((Bi, Ho, Wo, N), x)
     st = stats_buffer(M, N, x) if stats else None
     gemm(x, w, y, M, N, 9 * C, C, 9 * C, N, a_mode=A_CONV, stats=st, conv=(H, W, C), bias=bias, relu=relu,
-         precision=prec, a_amax=aa, b_amax=ba)
+         precision=prec, a_amax=aa, b_amax=ba, conv_stride=stride)
     return (y, st) if stats else y
+
+
+def conv3x3_dgrad_s2(dy, wt, H, W, prec=None, aa=None, ba=None):
+    """Data gradient of the 3x3 / stride 2 / pad 1 convolution: dy [B,Ho,Wo,N] -> dx [B,H,W,C] with wt [C, 9*N] =
+    weight_transpose(w, N, 9, C, flip=False).  Rows of the product are INPUT pixels; each gathers the taps of dy that reach
+    it (no zero-dilated copy of dy)."""
+    Bi, Ho, Wo, N = dy.shape
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise ValueError("conv3x3_dgrad_s2: dy %s is not the stride-2 output map of a %dx%d input" % (tuple(dy.shape), H, W))
+    C = wt.shape[0]
+    dx = empty((Bi, H, W, C), dy)
+    gemm(dy, wt, dx, Bi * H * W, C, 9 * N, N, 9 * N, C, a_mode=A_CONV, conv=(H, W, N), precision=prec, a_amax=aa, b_amax=ba,
+         conv_stride=2, conv_transposed=True)
+    return dx
 
 
 def fold_bn(w2d, st):
@@ -945,21 +968,24 @@ def conv1x1_wgrad(dy, x, prec=None, aa=None, ba=None):
     return matmul_tn(dy.reshape(-1, N), x.reshape(-1, C), prec=prec, aa=aa, ba=ba)
 
 
-def conv3x3_wgrad(dy, x, prec=None, aa=None, ba=None):
-    """dW [N, 9*C] for the 3x3/s1/p1 conv; dy [B,H,W,N], x [B,H,W,C]."""
+def conv3x3_wgrad(dy, x, prec=None, aa=None, ba=None, stride=1):
+    """dW [N, 9*C] for the 3x3/p1 conv of stride 1 or 2; dy [B,Ho,Wo,N], x [B,H,W,C]."""
     Bi, H, W, C = x.shape
     N = dy.shape[-1]
-    M = Bi * H * W
+    M = Bi * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+    if stride not in (1, 2) or dy.numel() != M * N:
+        raise ValueError("conv3x3_wgrad: dy %s does not match x %s at stride %s" % (tuple(dy.shape), tuple(x.shape), stride))
     J = 9 * C
     out = empty((N, J), x)
     tiles = ((N + 127) // 128) * ((J + 127) // 128)
     splits = _wgrad_splits(tiles, M)
     if splits == 1:
-        gemm(dy, x, out, N, J, M, N, C, J, a_mode=A_MC, b_mode=B_CONV, conv=(H, W, C), precision=prec, a_amax=aa, b_amax=ba)
+        gemm(dy, x, out, N, J, M, N, C, J, a_mode=A_MC, b_mode=B_CONV, conv=(H, W, C), precision=prec, a_amax=aa, b_amax=ba,
+             conv_stride=stride)
         return out
     slab = empty((splits, N, J), x)
     gemm(dy, x, slab, N, J, M, N, C, J, a_mode=A_MC, b_mode=B_CONV, conv=(H, W, C), splits=splits, strideSplit=N * J,
-         precision=prec, a_amax=aa, b_amax=ba)
+         precision=prec, a_amax=aa, b_amax=ba, conv_stride=stride)
     call("trid_slab_reduce_f32", _p(slab), _p(out), N * J, splits, N * J, 0, stream())
     return out
 
@@ -977,6 +1003,85 @@ def stem_im2col(img, ldcol=28):
     col = empty((Bi * Ho * Wo, ldcol), img)
     call("trid_stem_im2col_f32", _p(img), _p(col), Bi, Cin, H, W, Ho, Wo, ldcol, stream())
     return col, Ho, Wo
+
+
+# --------------------------------------------------------------------------- ImageNet ResNet pieces (csrc/resnet_ops.hip)
+def stem7_conv(images, w, stats=True):
+    """The ImageNet ResNet's stem convolution (3 -> 64 channels, 7x7, stride 2, pad 3) straight from the NCHW image batch:
+    y fp32 [B,Ho,Wo,64] (+ per-128-row (mean, M2) partials for bn_finalize)."""
+    Bi, Cin, Hi, Wi = images.shape
+    if Cin != 3 or tuple(w.shape) != (64, 3, 7, 7) or not w.is_contiguous() or not images.is_contiguous():
+        raise RuntimeError("stem7_conv: a contiguous [B,3,H,W] image batch and contiguous [64,3,7,7] filters are needed")
+    Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+    y = empty((Bi, Ho, Wo, 64), images)
+    st = stats_buffer(Bi * Ho * Wo, 64, images) if stats else None
+    call("trid_stem7_conv_f32", _p(images), _p(w), _p(y), _p(st), Bi, Hi, Wi, stream())
+    return (y, st) if stats else y
+
+
+def stem7_conv_wgrad(images, dy):
+    """Weight gradient of stem7_conv: dw [64,3,7,7] from the NCHW image batch and dy fp32 [B,Ho,Wo,64]."""
+    Bi, Cin, Hi, Wi = images.shape
+    Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+    if Cin != 3 or tuple(dy.shape) != (Bi, Ho, Wo, 64) or dy.dtype != torch.float32 or not dy.is_contiguous() or not images.is_contiguous():
+        raise RuntimeError("stem7_conv_wgrad: a contiguous [B,3,H,W] image batch and a contiguous fp32 [B,Ho,Wo,64] gradient are needed")
+    dw = empty((64, 3, 7, 7), images)
+    slabs = empty((_query("trid_stem7_conv_wgrad_slabs"), 64 * 147), images)
+    call("trid_stem7_conv_wgrad_f32", _p(images), _p(dy), _p(dw), _p(slabs), Bi, Hi, Wi, stream())
+    return dw
+
+
+def bn_relu_maxpool(y, st, amax=None):
+    """maxpool(3, stride 2, pad 1)(relu(bn(y))): y [B,H,W,C] -> [B,(H-1)//2+1,(W-1)//2+1,C]; amax as bn_apply."""
+    Bi, H, W, C = y.shape
+    out = empty((Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), y)
+    call("trid_bn_relu_maxpool_f32", _p(y), _p(st.scale), _p(st.shift), _p(out), Bi, H, W, C, _p(amax), stream())
+    return out
+
+
+def bn_relu_maxpool_bwd(g, y, st):
+    """Backward of bn_relu_maxpool's pool: g [B,Hp,Wp,C] -> the gradient with respect to relu(bn(y)), [B,H,W,C]
+    (bn_bwd(..., mask_mode=1) takes it next)."""
+    Bi, H, W, C = y.shape
+    if tuple(g.shape) != (Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C) or not g.is_contiguous():
+        raise RuntimeError("bn_relu_maxpool_bwd: g %s does not match y %s" % (tuple(g.shape), tuple(y.shape)))
+    dx = torch.empty_like(y)
+    call("trid_bn_relu_maxpool_bwd_f32", _p(g), _p(y), _p(st.scale), _p(st.shift), _p(dx), Bi, H, W, C, stream())
+    return dx
+
+
+def subsample2(x, amax=None):
+    """x [B,H,W,C] -> its even rows and columns [B,(H-1)//2+1,(W-1)//2+1,C] (the input of a stride-2 1x1 convolution)."""
+    Bi, H, W, C = x.shape
+    out = empty((Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), x)
+    call("trid_subsample2_f32", _p(x), _p(out), Bi, H, W, C, _p(amax), stream())
+    return out
+
+
+def subsample2_bwd(g, H, W):
+    """g [B,Ho,Wo,C] -> [B,H,W,C]: g at the even positions, zero elsewhere."""
+    Bi, Ho, Wo, C = g.shape
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1) or not g.is_contiguous():
+        raise RuntimeError("subsample2_bwd: g %s is not the subsampled map of a %dx%d input" % (tuple(g.shape), H, W))
+    dx = empty((Bi, H, W, C), g)
+    call("trid_subsample2_bwd_f32", _p(g), _p(dx), Bi, H, W, C, stream())
+    return dx
+
+
+def global_avgpool(x):
+    """x [B,H,W,C] -> [B,C], the mean over the pixels (summed in pixel order)."""
+    Bi, H, W, C = x.shape
+    out = empty((Bi, C), x)
+    call("trid_global_avgpool_f32", _p(x), _p(out), Bi, H * W, C, stream())
+    return out
+
+
+def global_avgpool_bwd(g, H, W):
+    """g [B,C] -> [B,H,W,C] = g / (H*W) at every pixel."""
+    Bi, C = g.shape
+    dx = empty((Bi, H, W, C), g)
+    call("trid_global_avgpool_bwd_f32", _p(g.contiguous()), _p(dx), Bi, H * W, C, stream())
+    return dx
 
 
 # --------------------------------------------------------------------------- BatchNorm
