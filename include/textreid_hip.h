@@ -522,6 +522,42 @@ int trid_gru_step_bwd_f32(const void* img_bwd, const float* w_amax, const float*
                           int Lmax, int L, int B, int H, long long gates_dstride, long long hprev_dstride,
                           long long dgh_dstride, void* stream);
 
+/* --- Stacked BiGRU (gru.py:36-43: nn.GRU(num_layers > 1, dropout = p); gru.py:77 runs every layer): the steps of a
+ * layer BELOW the last one.  Instead of the running max they emit the layer's output sequence yseq [B*L, 2H]: row
+ * b*L + t, column d*H + j = the new h where t < length[b], zero elsewhere (every row t < Lmax is written by exactly
+ * one step of each direction, so no fill is needed) - the row-major A operand (K = 2H) of the next layer's input
+ * projection.  The last layer of a stack runs trid_gru_step_* / trid_gru_cell_* above.
+ * trid_gru_step_seq_fwd_f32 / trid_gru_cell_seq_fwd_f32: as trid_gru_step_fwd_f32 / trid_gru_cell_fwd_f32 with yseq in
+ * place of maxv / argt (gates / hprev NULL when nothing is saved).
+ * trid_gru_step_seq_bwd_f32 / trid_gru_cell_seq_bwd_f32: as trid_gru_step_bwd_f32 / trid_gru_cell_bwd_f32 with the
+ * per-step output gradient dyseq [B*L, 2H] (read where t < length[b]) in place of dout where argt == t. */
+int trid_gru_step_seq_fwd_f32(const void* img_fwd, const float* w_amax, const void* hp_in, void* hp_out, float* h,
+                              const float* gi, const int64_t* lengths, float* gates, float* hprev, float* yseq, int s,
+                              int Lmax, int L, int B, int Bp, int H, long long gates_dstride, long long hprev_dstride,
+                              void* stream);
+int trid_gru_step_seq_bwd_f32(const void* img_bwd, const float* w_amax, const float* dgh_in, const float* amax_in,
+                              float* amax_out, const float* dyseq, const float* gates, const float* hprev,
+                              const int64_t* lengths, float* dh, float* dGi, float* dgh_out, int s, int Lmax, int L, int B,
+                              int H, long long gates_dstride, long long hprev_dstride, long long dgh_dstride, void* stream);
+int trid_gru_cell_seq_fwd_f32(const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
+                              float* hprev, float* yseq, int s, int Lmax, int L, int B, int Hd, long long gates_dstride,
+                              long long hprev_dstride, void* stream);
+int trid_gru_cell_seq_bwd_f32(const float* dyseq, const float* gates, const float* hprev, const int64_t* lengths,
+                              float* dh, float* dGi, float* dgh, int s, int Lmax, int L, int B, int Hd,
+                              long long gates_dstride, long long hprev_dstride, long long dgh_dstride, void* stream);
+/* Dropout between the layers of the stack (gru.py:40: nn.GRU(dropout = p) drops the output of every layer but the last,
+ * in training mode).  x[i] = y[i] * keep[i] / (1 - p) over n elements (x may alias y); keep[i] (uint8, 0 or 1) is written
+ * for the backward pass.  keep comes from Philox4x32-10: elements 4g .. 4g+3 take the four words of
+ * philox(counter = (g.lo, g.hi, o.lo, o.hi), key = (seed.lo, seed.hi)) with o = state[1] + draw, seed = state[0]; an
+ * element is kept iff its word >= floor(p * 2^32).  state = int64[2] (seed, offset) in DEVICE memory, read by the kernel:
+ * a recorded step draws a fresh mask on every replay.  draw = index of the mask within one forward.
+ * trid_dropout_seq_bwd_f32: dx[i] = dx[i] * keep[i] / (1 - p) in place.
+ * trid_dropout_advance: state[1] += draws (a one-thread launch, stream-ordered behind the masks of a forward). */
+int trid_dropout_seq_fwd_f32(const float* y, float* x, uint8_t* keep, long long n, float p, const int64_t* state,
+                             long long draw, void* stream);
+int trid_dropout_seq_bwd_f32(float* dx, const uint8_t* keep, long long n, float p, void* stream);
+int trid_dropout_advance(int64_t* state, long long draws, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Embedding head and losses (head.py:126-175, losses.py, moco_head/loss.py).
  * ------------------------------------------------------------------------- */

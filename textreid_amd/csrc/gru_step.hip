@@ -105,6 +105,7 @@ struct GruFwdParams {
     float* hprev;             // [2][.][B][H] slice of this step (or null)
     float* maxv;              // [B][2H]
     int* argt;                // [B][2H]
+    float* yseq;              // [B*L][2H] output sequence (SEQ form only: a layer below the last of a stack)
     int s, Lmax, L, B, Bp, H;
     long long gates_ds, hprev_ds;
 };
@@ -131,6 +132,11 @@ __device__ __forceinline__ void stage_image(uint4* __restrict__ dst, const uint4
     }
 }
 
+// SEQ (a layer below the last of a stacked GRU, nn.GRU num_layers > 1): instead of the running max the step writes its
+// output into yseq row b*L + t, column d*H + j - the new h where t < length, zero elsewhere - which is the row-major A
+// operand (K = 2H) of the next layer's input projection as it stands.  Every (b, t < Lmax, d) is written by exactly one
+// step, so the rows at t >= length come out zero under a bound_only batch too and the buffer needs no fill.
+template <bool SEQ>
 __global__ __launch_bounds__(GTHREADS) void gru_step_fwd_kernel(GruFwdParams p) {
     extern __shared__ __attribute__((aligned(16))) uint4 wsm[];  // [plane][gate][kstep][64]; later the K-slice partials
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -161,7 +167,8 @@ __global__ __launch_bounds__(GTHREADS) void gru_step_fwd_kernel(GruFwdParams p) 
     const float* gir = p.gi + ((long long)ebc * p.L + t) * (6 * H) + (long long)d * 3 * H;
     const float gr = gir[j], gz = gir[H + j], gn = gir[2 * H + j];
     const int mc = ebc * 2 * H + d * H + j;
-    const float cur = p.maxv[mc];
+    float cur = 0.f;
+    if constexpr (!SEQ) cur = p.maxv[mc];
     stage_image<6>(wsm, p.wimg + ((long long)d * (H / GU) + ub) * 2 * per_plane, 2 * per_plane, tid);
     v4f acc[3];
 #pragma unroll
@@ -228,11 +235,14 @@ __global__ __launch_bounds__(GTHREADS) void gru_step_fwd_kernel(GruFwdParams p) 
             float* gs = p.gates + (long long)d * p.gates_ds + (long long)eb * (4 * H);
             gs[j] = rg; gs[H + j] = zg; gs[2 * H + j] = ng; gs[3 * H + j] = hn_lin;
         }
-        if (d == 0 ? (hnew > cur) : (hnew >= cur)) {  // first index wins on ties: forward walks t upward, reverse downward
-            p.maxv[mc] = hnew;
-            p.argt[mc] = t;
+        if constexpr (!SEQ) {
+            if (d == 0 ? (hnew > cur) : (hnew >= cur)) {  // first index wins on ties: forward walks t upward, reverse downward
+                p.maxv[mc] = hnew;
+                p.argt[mc] = t;
+            }
         }
     }
+    if constexpr (SEQ) p.yseq[((long long)eb * p.L + t) * (2 * H) + d * H + j] = act ? hnew : 0.f;
     p.hp_out[((long long)d * p.Bp + eb) * H + j] = pack_hl(hnew * GH_SC);
 }
 
@@ -244,6 +254,7 @@ struct GruBwdParams {
     float* amax_out;        // [gridDim workgroups] receives this step's (no atomics: 2048 waves on one word cost 20 us)
     const float* dout;      // [B][2H]
     const int* argt;
+    const float* dyseq;     // [B*L][2H] gradient of the output sequence (SEQ form only)
     const float* gates;     // slices of this step
     const float* hprev;
     const long long* lengths;
@@ -254,6 +265,8 @@ struct GruBwdParams {
     long long gates_ds, hprev_ds, dgh_ds;
 };
 
+// SEQ: the per-step output gradient dyseq[b*L + t, d*H + j] (t < length) takes the place of the arg-max scatter of dout.
+template <bool SEQ>
 __global__ __launch_bounds__(GTHREADS) void gru_step_bwd_kernel(GruBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) uint4 wsm[];  // [plane][kstep over 3H][64]; later the K-slice partials
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -286,7 +299,9 @@ __global__ __launch_bounds__(GTHREADS) void gru_step_bwd_kernel(GruBwdParams p) 
     const float dh0 = p.dh[hidx];
     const bool act = (long long)t < p.lengths[ebc];
     const int mc = ebc * 2 * H + d * H + j;
-    const float dov = p.argt[mc] == t ? p.dout[mc] : 0.f;
+    float dov;
+    if constexpr (SEQ) dov = act ? p.dyseq[((long long)ebc * p.L + t) * (2 * H) + d * H + j] : 0.f;
+    else dov = p.argt[mc] == t ? p.dout[mc] : 0.f;
     const float* gs = p.gates + (long long)d * p.gates_ds + (long long)ebc * (4 * H);
     const float rg = gs[j], zg = gs[H + j], ng = gs[2 * H + j], hl = gs[3 * H + j];
     const float hpv = p.hprev[(long long)d * p.hprev_ds + (long long)ebc * H + j];
@@ -378,6 +393,74 @@ __global__ __launch_bounds__(GTHREADS) void gru_step_bwd_kernel(GruBwdParams p) 
     }
 }
 
+// ---- The unfused pair of a step (one batched GEMM h @ W_hh^T + one cell kernel: H outside 32..768, TRID_FUSED_GRU=0) in
+// the sequence form: as gru_cell_fwd_kernel / gru_cell_bwd_kernel (attn_text.hip), yseq / dyseq in place of the max.
+__device__ __forceinline__ float sigmoid_exact_(float v) { return 1.f / (1.f + expf(-v)); }
+
+__global__ void gru_cell_seq_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, float* __restrict__ h,
+                                        const int64_t* __restrict__ lengths, float* __restrict__ gates,
+                                        float* __restrict__ hprev, float* __restrict__ yseq, int s, int Lmax, int L, int B,
+                                        int Hd, long long gates_ds, long long hprev_ds) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2LL * B * Hd) return;
+    const int j = (int)(i % Hd);
+    const int b = (int)((i / Hd) % B);
+    const int d = (int)(i / ((long long)Hd * B));
+    const int t = d == 0 ? s : Lmax - 1 - s;
+    const bool active = (long long)t < lengths[b];
+    const float hp = h[i];
+    if (hprev != nullptr) hprev[(long long)d * hprev_ds + (long long)b * Hd + j] = hp;
+    float* yr = yseq + ((long long)b * L + t) * (2 * Hd) + (long long)d * Hd;
+    if (!active) {
+        yr[j] = 0.f;
+        return;
+    }
+    const float* gir = gi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
+    const float* ghr = gh + ((long long)d * B + b) * (3 * Hd);
+    const float r = sigmoid_exact_(gir[j] + ghr[j]);
+    const float z = sigmoid_exact_(gir[Hd + j] + ghr[Hd + j]);
+    const float hn_lin = ghr[2 * Hd + j];
+    const float n = tanhf(fmaf(r, hn_lin, gir[2 * Hd + j]));
+    const float hnew = (1.f - z) * n + z * hp;
+    h[i] = hnew;
+    if (gates != nullptr) {
+        float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
+        gs[j] = r; gs[Hd + j] = z; gs[2 * Hd + j] = n; gs[3 * Hd + j] = hn_lin;
+    }
+    yr[j] = hnew;
+}
+
+__global__ void gru_cell_seq_bwd_kernel(const float* __restrict__ dyseq, const float* __restrict__ gates,
+                                        const float* __restrict__ hprev, const int64_t* __restrict__ lengths,
+                                        float* __restrict__ dh, float* __restrict__ dGi, float* __restrict__ dgh, int s,
+                                        int Lmax, int L, int B, int Hd, long long gates_ds, long long hprev_ds,
+                                        long long dgh_ds) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2LL * B * Hd) return;
+    const int j = (int)(i % Hd);
+    const int b = (int)((i / Hd) % B);
+    const int d = (int)(i / ((long long)Hd * B));
+    const int t = d == 0 ? s : Lmax - 1 - s;
+    const bool active = (long long)t < lengths[b];
+    float* dgir = dGi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
+    float* dghr = dgh + (long long)d * dgh_ds + (long long)b * (3 * Hd);
+    if (!active) {
+        dgir[j] = 0.f; dgir[Hd + j] = 0.f; dgir[2 * Hd + j] = 0.f;
+        dghr[j] = 0.f; dghr[Hd + j] = 0.f; dghr[2 * Hd + j] = 0.f;
+        return;
+    }
+    const float dhv = dh[i] + dyseq[((long long)b * L + t) * (2 * Hd) + (long long)d * Hd + j];
+    const float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
+    const float r = gs[j], z = gs[Hd + j], n = gs[2 * Hd + j], hn_lin = gs[3 * Hd + j];
+    const float hp = hprev[(long long)d * hprev_ds + (long long)b * Hd + j];
+    const float dn_pre = dhv * (1.f - z) * (1.f - n * n);
+    const float dz_pre = dhv * (hp - n) * z * (1.f - z);
+    const float dr_pre = dn_pre * hn_lin * r * (1.f - r);
+    dgir[j] = dr_pre; dgir[Hd + j] = dz_pre; dgir[2 * Hd + j] = dn_pre;
+    dghr[j] = dr_pre; dghr[Hd + j] = dz_pre; dghr[2 * Hd + j] = dn_pre * r;
+    dh[i] = dhv * z;
+}
+
 static bool gru_step_shape_ok(int B, int H) { return B > 0 && H >= 32 && H % 32 == 0 && H <= 768; }
 
 }  // namespace trid
@@ -417,28 +500,75 @@ static int gru_lds_attr(const void* fn, size_t lds, const char* what) {
     return TRID_OK;
 }
 
+// the two forms of a forward step share everything but the kernel instantiation and its (maxv, argt) / yseq outputs
+template <bool SEQ>
+static int launch_step_fwd(const char* what, const void* img_fwd, const float* w_amax, const void* hp_in, void* hp_out, float* h,
+                           const float* gi, const int64_t* lengths, float* gates, float* hprev, float* maxv, int32_t* argt,
+                           float* yseq, int s, int Lmax, int L, int B, int Bp, int H, long long gates_dstride,
+                           long long hprev_dstride, void* stream) {
+    TRID_REQUIRE(img_fwd && w_amax && hp_in && hp_out && h && gi && lengths && (SEQ ? yseq != nullptr : (maxv && argt)), "%s: null pointer", what);
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Bp >= B && Bp % 16 == 0, "%s: bad step/shape", what);
+    if (!gru_step_shape_ok(B, H)) {
+        set_error("%s: built for H %% 32 == 0, 32 <= H <= 768 (got %d)", what, H);
+        return TRID_E_UNSUPPORTED;
+    }
+    TRID_REQUIRE(aligned16(img_fwd) && aligned16(hp_in) && aligned16(hp_out), "%s: images / packed state must be 16-byte aligned", what);
+    static std::once_flag once;  // (one per instantiation)
+    static int attr_rc = TRID_OK;
+    std::call_once(once, [what] { attr_rc = gru_lds_attr((const void*)gru_step_fwd_kernel<SEQ>, 768 * 192, what); });
+    if (attr_rc != TRID_OK) return attr_rc;
+    GruFwdParams p;
+    p.wimg = (const uint4*)img_fwd; p.w_amax = w_amax; p.hp_in = (const unsigned*)hp_in; p.hp_out = (unsigned*)hp_out; p.h = h;
+    p.gi = gi; p.lengths = (const long long*)lengths; p.gates = gates; p.hprev = hprev; p.maxv = maxv; p.argt = argt; p.yseq = yseq;
+    p.s = s; p.Lmax = Lmax; p.L = L; p.B = B; p.Bp = Bp; p.H = H; p.gates_ds = gates_dstride; p.hprev_ds = hprev_dstride;
+    const size_t lds = std::max<size_t>((size_t)H * 192, GKQ * 3 * GMB * GU * sizeof(float));
+    hipLaunchKernelGGL(gru_step_fwd_kernel<SEQ>, dim3(H / GU, 2, (B + GMB - 1) / GMB), dim3(GTHREADS), lds, (hipStream_t)stream, p);
+    return check_launch(what);
+}
+
 extern "C" int trid_gru_step_fwd_f32(const void* img_fwd, const float* w_amax, const void* hp_in, void* hp_out, float* h,
                                      const float* gi, const int64_t* lengths, float* gates, float* hprev, float* maxv,
                                      int32_t* argt, int s, int Lmax, int L, int B, int Bp, int H, long long gates_dstride,
                                      long long hprev_dstride, void* stream) {
-    TRID_REQUIRE(img_fwd && w_amax && hp_in && hp_out && h && gi && lengths && maxv && argt, "trid_gru_step_fwd_f32: null pointer");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Bp >= B && Bp % 16 == 0, "trid_gru_step_fwd_f32: bad step/shape");
+    return launch_step_fwd<false>("trid_gru_step_fwd_f32", img_fwd, w_amax, hp_in, hp_out, h, gi, lengths, gates, hprev, maxv, argt,
+                                  nullptr, s, Lmax, L, B, Bp, H, gates_dstride, hprev_dstride, stream);
+}
+
+extern "C" int trid_gru_step_seq_fwd_f32(const void* img_fwd, const float* w_amax, const void* hp_in, void* hp_out, float* h,
+                                         const float* gi, const int64_t* lengths, float* gates, float* hprev, float* yseq,
+                                         int s, int Lmax, int L, int B, int Bp, int H, long long gates_dstride,
+                                         long long hprev_dstride, void* stream) {
+    return launch_step_fwd<true>("trid_gru_step_seq_fwd_f32", img_fwd, w_amax, hp_in, hp_out, h, gi, lengths, gates, hprev, nullptr,
+                                 nullptr, yseq, s, Lmax, L, B, Bp, H, gates_dstride, hprev_dstride, stream);
+}
+
+template <bool SEQ>
+static int launch_step_bwd(const char* what, const void* img_bwd, const float* w_amax, const float* dgh_in, const float* amax_in,
+                           float* amax_out, const float* dout, const int32_t* argt, const float* dyseq, const float* gates,
+                           const float* hprev, const int64_t* lengths, float* dh, float* dGi, float* dgh_out, int s, int Lmax,
+                           int L, int B, int H, long long gates_dstride, long long hprev_dstride, long long dgh_dstride,
+                           void* stream) {
+    TRID_REQUIRE(img_bwd && w_amax && amax_out && (SEQ ? dyseq != nullptr : (dout && argt)) && gates && hprev && lengths && dh && dGi && dgh_out,
+                 "%s: null pointer", what);
+    TRID_REQUIRE((dgh_in == nullptr) == (amax_in == nullptr), "%s: dgh_in and amax_in come together", what);
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0, "%s: bad step/shape", what);
     if (!gru_step_shape_ok(B, H)) {
-        set_error("trid_gru_step_fwd_f32: built for H %% 32 == 0, 32 <= H <= 768 (got %d)", H);
+        set_error("%s: built for H %% 32 == 0, 32 <= H <= 768 (got %d)", what, H);
         return TRID_E_UNSUPPORTED;
     }
-    TRID_REQUIRE(aligned16(img_fwd) && aligned16(hp_in) && aligned16(hp_out), "trid_gru_step_fwd_f32: images / packed state must be 16-byte aligned");
-    static std::once_flag once;
+    TRID_REQUIRE(aligned16(img_bwd) && (dgh_in == nullptr || aligned16(dgh_in)), "%s: image / dgh must be 16-byte aligned", what);
+    static std::once_flag once;  // (one per instantiation)
     static int attr_rc = TRID_OK;
-    std::call_once(once, [] { attr_rc = gru_lds_attr((const void*)gru_step_fwd_kernel, 768 * 192, "trid_gru_step_fwd_f32"); });
+    std::call_once(once, [what] { attr_rc = gru_lds_attr((const void*)gru_step_bwd_kernel<SEQ>, 768 * 192, what); });
     if (attr_rc != TRID_OK) return attr_rc;
-    GruFwdParams p;
-    p.wimg = (const uint4*)img_fwd; p.w_amax = w_amax; p.hp_in = (const unsigned*)hp_in; p.hp_out = (unsigned*)hp_out; p.h = h;
-    p.gi = gi; p.lengths = (const long long*)lengths; p.gates = gates; p.hprev = hprev; p.maxv = maxv; p.argt = argt;
-    p.s = s; p.Lmax = Lmax; p.L = L; p.B = B; p.Bp = Bp; p.H = H; p.gates_ds = gates_dstride; p.hprev_ds = hprev_dstride;
-    const size_t lds = std::max<size_t>((size_t)H * 192, GKQ * 3 * GMB * GU * sizeof(float));
-    hipLaunchKernelGGL(gru_step_fwd_kernel, dim3(H / GU, 2, (B + GMB - 1) / GMB), dim3(GTHREADS), lds, (hipStream_t)stream, p);
-    return check_launch("trid_gru_step_fwd_f32");
+    GruBwdParams p;
+    p.wimg = (const uint4*)img_bwd; p.w_amax = w_amax; p.dgh_in = dgh_in; p.amax_in = amax_in; p.amax_out = amax_out;
+    p.dout = dout; p.argt = argt; p.dyseq = dyseq; p.gates = gates; p.hprev = hprev; p.lengths = (const long long*)lengths; p.dh = dh;
+    p.dGi = dGi; p.dgh_out = dgh_out; p.s = s; p.Lmax = Lmax; p.L = L; p.B = B; p.H = H;
+    p.gates_ds = gates_dstride; p.hprev_ds = hprev_dstride; p.dgh_ds = dgh_dstride;
+    const size_t lds = std::max<size_t>((size_t)H * 192, GKQ * GMB * GU * sizeof(float));
+    hipLaunchKernelGGL(gru_step_bwd_kernel<SEQ>, dim3(H / GU, 2, (B + GMB - 1) / GMB), dim3(GTHREADS), lds, (hipStream_t)stream, p);
+    return check_launch(what);
 }
 
 extern "C" int trid_gru_step_bwd_f32(const void* img_bwd, const float* w_amax, const float* dgh_in, const float* amax_in,
@@ -446,25 +576,37 @@ extern "C" int trid_gru_step_bwd_f32(const void* img_bwd, const float* w_amax, c
                                      const float* hprev, const int64_t* lengths, float* dh, float* dGi, float* dgh_out, int s,
                                      int Lmax, int L, int B, int H, long long gates_dstride, long long hprev_dstride,
                                      long long dgh_dstride, void* stream) {
-    TRID_REQUIRE(img_bwd && w_amax && amax_out && dout && argt && gates && hprev && lengths && dh && dGi && dgh_out,
-                 "trid_gru_step_bwd_f32: null pointer");
-    TRID_REQUIRE((dgh_in == nullptr) == (amax_in == nullptr), "trid_gru_step_bwd_f32: dgh_in and amax_in come together");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0, "trid_gru_step_bwd_f32: bad step/shape");
-    if (!gru_step_shape_ok(B, H)) {
-        set_error("trid_gru_step_bwd_f32: built for H %% 32 == 0, 32 <= H <= 768 (got %d)", H);
-        return TRID_E_UNSUPPORTED;
-    }
-    TRID_REQUIRE(aligned16(img_bwd) && (dgh_in == nullptr || aligned16(dgh_in)), "trid_gru_step_bwd_f32: image / dgh must be 16-byte aligned");
-    static std::once_flag once;
-    static int attr_rc = TRID_OK;
-    std::call_once(once, [] { attr_rc = gru_lds_attr((const void*)gru_step_bwd_kernel, 768 * 192, "trid_gru_step_bwd_f32"); });
-    if (attr_rc != TRID_OK) return attr_rc;
-    GruBwdParams p;
-    p.wimg = (const uint4*)img_bwd; p.w_amax = w_amax; p.dgh_in = dgh_in; p.amax_in = amax_in; p.amax_out = amax_out;
-    p.dout = dout; p.argt = argt; p.gates = gates; p.hprev = hprev; p.lengths = (const long long*)lengths; p.dh = dh;
-    p.dGi = dGi; p.dgh_out = dgh_out; p.s = s; p.Lmax = Lmax; p.L = L; p.B = B; p.H = H;
-    p.gates_ds = gates_dstride; p.hprev_ds = hprev_dstride; p.dgh_ds = dgh_dstride;
-    const size_t lds = std::max<size_t>((size_t)H * 192, GKQ * GMB * GU * sizeof(float));
-    hipLaunchKernelGGL(gru_step_bwd_kernel, dim3(H / GU, 2, (B + GMB - 1) / GMB), dim3(GTHREADS), lds, (hipStream_t)stream, p);
-    return check_launch("trid_gru_step_bwd_f32");
+    return launch_step_bwd<false>("trid_gru_step_bwd_f32", img_bwd, w_amax, dgh_in, amax_in, amax_out, dout, argt, nullptr, gates, hprev,
+                                  lengths, dh, dGi, dgh_out, s, Lmax, L, B, H, gates_dstride, hprev_dstride, dgh_dstride, stream);
+}
+
+extern "C" int trid_gru_step_seq_bwd_f32(const void* img_bwd, const float* w_amax, const float* dgh_in, const float* amax_in,
+                                         float* amax_out, const float* dyseq, const float* gates, const float* hprev,
+                                         const int64_t* lengths, float* dh, float* dGi, float* dgh_out, int s, int Lmax, int L,
+                                         int B, int H, long long gates_dstride, long long hprev_dstride, long long dgh_dstride,
+                                         void* stream) {
+    return launch_step_bwd<true>("trid_gru_step_seq_bwd_f32", img_bwd, w_amax, dgh_in, amax_in, amax_out, nullptr, nullptr, dyseq, gates,
+                                 hprev, lengths, dh, dGi, dgh_out, s, Lmax, L, B, H, gates_dstride, hprev_dstride, dgh_dstride, stream);
+}
+
+extern "C" int trid_gru_cell_seq_fwd_f32(const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
+                                         float* hprev, float* yseq, int s, int Lmax, int L, int B, int Hd,
+                                         long long gates_dstride, long long hprev_dstride, void* stream) {
+    TRID_REQUIRE(gi && gh && h && lengths && yseq, "trid_gru_cell_seq_fwd_f32: null pointer");
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_seq_fwd_f32: bad step/shape");
+    const long long n = 2LL * B * Hd;
+    hipLaunchKernelGGL(gru_cell_seq_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi, gh, h, lengths,
+                       gates, hprev, yseq, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride);
+    return check_launch("trid_gru_cell_seq_fwd_f32");
+}
+
+extern "C" int trid_gru_cell_seq_bwd_f32(const float* dyseq, const float* gates, const float* hprev, const int64_t* lengths,
+                                         float* dh, float* dGi, float* dgh, int s, int Lmax, int L, int B, int Hd,
+                                         long long gates_dstride, long long hprev_dstride, long long dgh_dstride, void* stream) {
+    TRID_REQUIRE(dyseq && gates && hprev && lengths && dh && dGi && dgh, "trid_gru_cell_seq_bwd_f32: null pointer");
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_seq_bwd_f32: bad step/shape");
+    const long long n = 2LL * B * Hd;
+    hipLaunchKernelGGL(gru_cell_seq_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dyseq, gates, hprev,
+                       lengths, dh, dGi, dgh, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride, dgh_dstride);
+    return check_launch("trid_gru_cell_seq_bwd_f32");
 }
