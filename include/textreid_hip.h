@@ -689,6 +689,15 @@ int trid_adam_multi_f32(const uint64_t* p_ptrs, const uint64_t* g_ptrs, const ui
                         const int32_t* chunk_tensor, const int64_t* chunk_off, int n_chunks, int chunk_len,
                         float beta1, float beta2, float eps, const float* bias_c1, const float* bias_c2, int decoupled,
                         void* stream);
+/* Multi-tensor SGD step (torch.optim.SGD semantics with maximize=False, lib/solver/build.py:19-22: per-tensor lr and
+ * weight decay).  Per element: d = g + wd*w (d = g when wd == 0); buf = moms[i]*buf + gscale[i]*d; u = nesterov ?
+ * d + momentum*buf : buf; w -= lr*u - every product and sum rounded on its own.  lrs / wds / moms / gscale: DEVICE
+ * arrays, one entry per tensor; torch's first update of a parameter (buf = d) is moms[i] = 0, gscale[i] = 1 over a
+ * zero-filled buffer, later ones momentum, 1 - dampening.  buf_ptrs NULL: no momentum (moms / gscale unused). */
+int trid_sgd_multi_f32(const uint64_t* p_ptrs, const uint64_t* g_ptrs, const uint64_t* buf_ptrs, const int64_t* sizes,
+                       const float* lrs, const float* wds, const float* moms, const float* gscale,
+                       const int32_t* chunk_tensor, const int64_t* chunk_off, int n_chunks, int chunk_len,
+                       float momentum, int nesterov, void* stream);
 /* Ring-buffer push at device-resident pointer: queue row-major [K, C]
  * (transpose of the reference's [C,K], so the push is one contiguous slab). */
 int trid_enqueue_f32(float* v_queue, float* t_queue, int64_t* id_queue, int64_t* ptr, const float* v_keys,

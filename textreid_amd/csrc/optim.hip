@@ -1,9 +1,10 @@
 // MoCo state kernels: multi-tensor momentum (EMA) update of the key encoders
 // (head.py:73-94), ring-buffer enqueue with a device-resident pointer
 // (head.py:96-109), and a multi-tensor Adam step with per-tensor lr / weight
-// decay (lib/solver/build.py:6-40 creates one param group per tensor).
+// decay (lib/solver/build.py:6-40 creates one param group per tensor), and the
+// multi-tensor SGD step of the same rule (lib/solver/build.py:19-22).
 // All HBM-bound: one launch streams every tensor through a chunk table instead
-// of 178 (EMA) / 183 (Adam) x several tiny launches.
+// of 178 (EMA) / 183 (Adam, SGD) x several tiny launches.
 
 #include "common.h"
 
@@ -76,6 +77,90 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const uint64_t* __restr
     }
 }
 
+// torch.optim.SGD (maximize=False), one element or four.  Every product and sum is rounded on its own (-ffp-contract=off,
+// no fmaf): with wd == 0 and gs == 1 the buffer is torch's mul_ then add_ with alpha 1, bit for bit.
+typedef float sgd_f4 __attribute__((ext_vector_type(4)));
+// (the tables hold plain integers: told that they are global addresses the compiler emits global_, not flat_, accesses)
+typedef __attribute__((address_space(1))) float sgd_gf;
+typedef __attribute__((address_space(1))) sgd_f4 sgd_gf4;
+
+template <bool MOM, typename T>
+__device__ __forceinline__ void sgd_elem(T& w, const T g, T& b, float lr, float wd, float mom, float gs, float momentum,
+                                         int nesterov) {
+    T d = g;
+    if (wd != 0.f) d = g + wd * w;
+    T u = d;
+    if (MOM) {
+        b = mom * b + gs * d;
+        if (nesterov) u = d + momentum * b; else u = b;
+    }
+    w = w - lr * u;
+}
+
+// 12 B read + 8 B written per element (8 + 4 without momentum).  A chunk is one block's work: 16-byte accesses when the
+// chunk's three bases allow it (chunk offsets are multiples of 4 elements, so that is the tensors' own alignment), four
+// of them in flight per thread and array; the scalar loop otherwise.
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const uint64_t* __restrict__ p_ptrs,
+                                                        const uint64_t* __restrict__ g_ptrs,
+                                                        const uint64_t* __restrict__ buf_ptrs,
+                                                        const int64_t* __restrict__ sizes, const float* __restrict__ lrs,
+                                                        const float* __restrict__ wds, const float* __restrict__ moms,
+                                                        const float* __restrict__ gscale,
+                                                        const int32_t* __restrict__ chunk_tensor,
+                                                        const int64_t* __restrict__ chunk_off, int chunk_len,
+                                                        float momentum, int nesterov) {
+    const int c = blockIdx.x;
+    const int ti = chunk_tensor[c];
+    const long long off = chunk_off[c];
+    sgd_gf* __restrict__ p = reinterpret_cast<sgd_gf*>(p_ptrs[ti]) + off;
+    const sgd_gf* __restrict__ g = reinterpret_cast<const sgd_gf*>(g_ptrs[ti]) + off;
+    sgd_gf* __restrict__ bu = MOM ? reinterpret_cast<sgd_gf*>(buf_ptrs[ti]) + off : nullptr;
+    long long n = sizes[ti] - off;
+    if (n > chunk_len) n = chunk_len;
+    const float lr = lrs[ti], wd = wds[ti];
+    const float mom = MOM ? moms[ti] : 0.f, gs = MOM ? gscale[ti] : 1.f;
+    uint64_t bits = p_ptrs[ti] | g_ptrs[ti];  // (chunk offsets keep the tensors' 16-byte alignment)
+    if (MOM) bits |= buf_ptrs[ti];
+    long long k = threadIdx.x;  // first element of the scalar loop
+    if ((bits & 15u) == 0) {
+        constexpr int U = 4;
+        const long long n4 = n >> 2;
+        sgd_gf4* __restrict__ p4 = reinterpret_cast<sgd_gf4*>(p);
+        const sgd_gf4* __restrict__ g4 = reinterpret_cast<const sgd_gf4*>(g);
+        sgd_gf4* __restrict__ b4 = reinterpret_cast<sgd_gf4*>(bu);
+        long long i = threadIdx.x;
+        for (; i + 256 * (U - 1) < n4; i += 256 * U) {
+            sgd_f4 w[U], gr[U], b[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                w[j] = p4[i + 256 * j];
+                gr[j] = g4[i + 256 * j];
+                b[j] = MOM ? b4[i + 256 * j] : sgd_f4(0.f);
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                sgd_elem<MOM>(w[j], gr[j], b[j], lr, wd, mom, gs, momentum, nesterov);
+                if (MOM) b4[i + 256 * j] = b[j];
+                p4[i + 256 * j] = w[j];
+            }
+        }
+        for (; i < n4; i += 256) {
+            sgd_f4 w = p4[i], b = MOM ? b4[i] : sgd_f4(0.f);
+            sgd_elem<MOM>(w, sgd_f4(g4[i]), b, lr, wd, mom, gs, momentum, nesterov);
+            if (MOM) b4[i] = b;
+            p4[i] = w;
+        }
+        k += n4 << 2;  // the ragged tail (n is no multiple of 4 in a tensor's last chunk only)
+    }
+    for (; k < n; k += 256) {
+        float w = p[k], b = MOM ? bu[k] : 0.f;
+        sgd_elem<MOM>(w, float(g[k]), b, lr, wd, mom, gs, momentum, nesterov);
+        if (MOM) bu[k] = b;
+        p[k] = w;
+    }
+}
+
 __global__ void enqueue_kernel(float* __restrict__ vq, float* __restrict__ tq, int64_t* __restrict__ idq,
                                const int64_t* __restrict__ ptr, const float* __restrict__ vk,
                                const float* __restrict__ tk, const int64_t* __restrict__ ids, int K, int C, int B) {
@@ -122,6 +207,23 @@ extern "C" int trid_adam_multi_f32(const uint64_t* p_ptrs, const uint64_t* g_ptr
     hipLaunchKernelGGL(adam_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, p_ptrs, g_ptrs, m_ptrs, v_ptrs,
                        sizes, lrs, wds, chunk_tensor, chunk_off, chunk_len, beta1, beta2, eps, bias_c1, bias_c2, decoupled);
     return check_launch("trid_adam_multi_f32");
+}
+
+extern "C" int trid_sgd_multi_f32(const uint64_t* p_ptrs, const uint64_t* g_ptrs, const uint64_t* buf_ptrs,
+                                  const int64_t* sizes, const float* lrs, const float* wds, const float* moms,
+                                  const float* gscale, const int32_t* chunk_tensor, const int64_t* chunk_off,
+                                  int n_chunks, int chunk_len, float momentum, int nesterov, void* stream) {
+    TRID_REQUIRE(p_ptrs && g_ptrs && sizes && lrs && wds && chunk_tensor && chunk_off, "trid_sgd_multi_f32: null pointer");
+    TRID_REQUIRE(!buf_ptrs || (moms && gscale), "trid_sgd_multi_f32: momentum buffers need the moms / gscale tables");
+    TRID_REQUIRE(buf_ptrs || !nesterov, "trid_sgd_multi_f32: nesterov needs momentum buffers");
+    TRID_REQUIRE(n_chunks > 0 && chunk_len > 0 && chunk_len % 4 == 0, "trid_sgd_multi_f32: bad arguments");
+    if (buf_ptrs)
+        hipLaunchKernelGGL(sgd_multi_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, p_ptrs, g_ptrs, buf_ptrs,
+                           sizes, lrs, wds, moms, gscale, chunk_tensor, chunk_off, chunk_len, momentum, nesterov);
+    else
+        hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, p_ptrs, g_ptrs, buf_ptrs,
+                           sizes, lrs, wds, moms, gscale, chunk_tensor, chunk_off, chunk_len, momentum, nesterov);
+    return check_launch("trid_sgd_multi_f32");
 }
 
 extern "C" int trid_enqueue_f32(float* v_queue, float* t_queue, int64_t* id_queue, int64_t* ptr, const float* v_keys,

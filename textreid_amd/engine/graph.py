@@ -9,7 +9,8 @@ is recorded once with ``torch.cuda.graph`` and replayed: one host call per step.
 What varies between steps lives in device memory that the replay reads:
   * inputs: copied into static buffers (stream-ordered, before the replay);
   * MoCo queue pointer, BatchNorm counters, amax scalars: device-resident already;
-  * optimizer hyper-parameters and bias corrections: ``FusedAdam.advance_for_replay()``.
+  * optimizer hyper-parameters: ``advance_for_replay()`` of the fused optimizer - lr / weight decay of every group, and
+    ``FusedAdam``'s bias corrections or ``FusedSGD``'s buffer coefficient / gradient scale (its first-update encoding).
 
 Shapes are part of the recording: a batch of another shape (or another caption length bound) runs EAGERLY, with a
 warning - never silently through a graph recorded for different sizes.
@@ -29,6 +30,12 @@ import torch
 
 from ..caption import CaptionBatch
 from ..parallel import dp_active
+
+
+def implements_capture_protocol(optimizer):
+    """The recorded step drives its optimizer through prepare_capture / finish_capture / advance_for_replay
+    (solver.FusedAdam, solver.FusedSGD)."""
+    return all(callable(getattr(optimizer, m, None)) for m in ("prepare_capture", "finish_capture", "advance_for_replay"))
 
 
 class CapturedTrainStep:
@@ -62,10 +69,10 @@ class CapturedTrainStep:
         self.static = None
         self.out = None
         self.signature = None
-        self.plan = None         # the optimizer's pointer tables the recorded Adam launch reads (kept alive with the graph)
+        self.plan = None         # the optimizer's pointer tables the recorded optimizer launch reads (kept alive with the graph)
         self.disabled = False    # a failed capture: stay eager for the rest of the run
         self.recaptures = 0
-        self.adam_cap = None     # FusedAdam's table set of THIS recording
+        self.opt_cap = None     # the fused optimizer's table set of THIS recording
         self.cuts = []           # data parallel: the collectives of the recorded step, in marker order (parallel.Cut)
         self.cut_bytes = (0, 0)  # bytes of them staged from inside backward / issued after it (the reducer's accounting)
         self.log = logging.getLogger("PersonSearch.trainer")
@@ -101,8 +108,6 @@ class CapturedTrainStep:
         return (tuple(images.shape), tuple(cb.tokens.shape), cb.ids is not None)
 
     def _capture(self, images, cb):
-        from ..solver import FusedAdam
-
         self.static = {
             "images": images.clone(),
             "tokens": cb.tokens.clone(),
@@ -111,9 +116,10 @@ class CapturedTrainStep:
         }
         self.bound = int(self.caption_bound) if self.caption_bound is not None else int(cb.tokens.shape[1])
         scb = CaptionBatch(self.static["tokens"], self.static["lengths"], self.static["ids"], max_len=self.bound, bound_only=True)
-        self.adam_cap = None
-        if isinstance(self.optimizer, FusedAdam):
-            self.adam_cap = self.optimizer.prepare_capture(defer_table_copy=True)  # this recording's own table set
+        self.opt_cap = None
+        fused = self.optimizer is not None and implements_capture_protocol(self.optimizer)
+        if fused:
+            self.opt_cap = self.optimizer.prepare_capture(defer_table_copy=True)  # this recording's own table set
         elif self.optimizer is not None:
             raise RuntimeError("CapturedTrainStep needs textreid_amd.solver.FusedAdam (or optimizer=None)")
         for p in self.model.parameters():
@@ -157,11 +163,11 @@ class CapturedTrainStep:
             self.reducer.bytes_staged, self.reducer.bytes_post, self.reducer.steps = b0
         self.graph, self.out = g, {k: v.detach() for k, v in loss_dict.items()}
         del loss_dict, losses
-        if isinstance(self.optimizer, FusedAdam):
-            self.optimizer.finish_capture(self.adam_cap)  # the gradient address table of the recorded Adam launch: copied once, here
+        if fused:
+            self.optimizer.finish_capture(self.opt_cap)  # the gradient address table of the recorded optimizer launch: copied once, here
         self.grads = [(p, p.grad) for p in self.model.parameters() if p.grad is not None]  # live in the graph's pool
         self.signature = self._sig(images, cb)
-        # the recorded Adam launch has the ADDRESSES of this plan's tables baked in: hold it (so the allocator cannot
+        # the recorded optimizer launch has the ADDRESSES of this plan's tables baked in: hold it (so the allocator cannot
         # recycle them under the graph) and replay only while the optimizer still uses this very object
         self.plan = getattr(self.optimizer, "_plan", None)
         if self.launch == "streams":
@@ -325,7 +331,7 @@ class CapturedTrainStep:
             if p.grad is not g:
                 p.grad = g
         if self.optimizer is not None:
-            self.optimizer.advance_for_replay(self.adam_cap)
+            self.optimizer.advance_for_replay(self.opt_cap)
         from .. import ops
 
         if self.cuts:

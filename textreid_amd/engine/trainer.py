@@ -32,8 +32,8 @@ def train_step(model, optimizer, images, captions, reducer=None, pre_gather=None
 
 def do_train(model, data_loader, data_loader_val, optimizer, scheduler, checkpointer, meters, device,
              checkpoint_period, evaluate_period, arguments, log_period=20, capture=True):
-    """capture: record the step as one hipGraph after two eager steps (engine/graph.py) when the optimizer is the fused
-    Adam, the model runs on a GPU and there is one process; batches of another shape run eagerly."""
+    """capture: record the step as one hipGraph after two eager steps (engine/graph.py) when the optimizer is a fused one
+    (solver.FusedAdam, solver.FusedSGD) and the model runs on a GPU; batches of another shape run eagerly."""
     logger = logging.getLogger("PersonSearch.trainer")
     logger.info("Start training")
     max_epoch, epoch, iteration = arguments["max_epoch"], arguments["epoch"], arguments["iteration"]
@@ -61,10 +61,9 @@ def do_train(model, data_loader, data_loader_val, optimizer, scheduler, checkpoi
     # TRID_DP_CAPTURE=0: the eager data-parallel step (A/B runs).
     dp_capture = os.environ.get("TRID_DP_CAPTURE", "1") != "0"
     if capture and (not dp_active() or dp_capture) and torch.device(device).type == "cuda":
-        from ..solver import FusedAdam
-        from .graph import BucketedTrainStep
+        from .graph import BucketedTrainStep, implements_capture_protocol
 
-        if isinstance(optimizer, FusedAdam):
+        if implements_capture_protocol(optimizer):
             # one recording per caption bucket (32 / 48 / 64 / 105 recurrence steps; TRID_CAPTION_BUCKETS overrides): a batch runs
             # the recording of the smallest bucket that holds its longest caption
             runner = BucketedTrainStep(model, optimizer, warmup=2, reducer=reducer if dp_active() else None, pre_gather=pre_gather)

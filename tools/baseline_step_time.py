@@ -4,6 +4,8 @@
 Prints one JSON line.  Information only: compare with `python bench.py` (the MoCo step) from the same session.
 
 Usage:  python tools/baseline_step_time.py [--visual m_resnet50|m_resnet101|resnet50|resnet101] [--batch 128] [--warmup 5] [--steps 20]
+                                           [--optimizer Adam|AdamW|SGD] [--eager]
+(--optimizer: SOLVER.OPTIMIZER of the run; --eager: the eager step only)
 (resnet50 / resnet101: the ImageNet ResNet of baseline_gru_rn50_ls_bs128.yaml, built from config.imagenet_cfg, 12000-word vocabulary)
 """
 import argparse
@@ -30,6 +32,7 @@ def run(mode, args, dev):
     cfg = imagenet_cfg(args.visual) if imagenet else baseline_cfg(args.visual)
     model = build_model(cfg, vocab_dict=None if imagenet else torch.randn(49408, 512) * 0.02).to(dev).train()
     vocab = cfg.MODEL.GRU.VOCABULARY_SIZE if imagenet else 49408
+    cfg.SOLVER.OPTIMIZER = args.optimizer
     opt = make_optimizer(cfg, model)
     runner = CapturedTrainStep(model, opt, warmup=2, caption_bound=64)
     batches = [tuple(x.to(dev) for x in synth_batch(args.batch, s, 3)) for s in range(4)]
@@ -58,10 +61,14 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--optimizer", default="Adam", choices=["Adam", "AdamW", "SGD"])
+    ap.add_argument("--eager", action="store_true", help="time the eager step only")
     args = ap.parse_args()
     dev = torch.device("cuda")
     out = {"workload": "baseline_step", "visual": args.visual, "batch": args.batch, "warmup": args.warmup, "steps": args.steps}
-    for mode in ("eager", "captured"):
+    if args.optimizer != "Adam":
+        out["optimizer"] = args.optimizer
+    for mode in ("eager",) if args.eager else ("eager", "captured"):
         out[mode] = run(mode, args, dev)
     print(json.dumps(out))
 
