@@ -750,6 +750,46 @@ int trid_argsort_rows_desc_f32(const float* sim, int ld, int Q, int G, int64_t* 
 int trid_rank_metrics(const int64_t* indices, const int64_t* q_pids, const int64_t* g_pids, int Q, int R,
                       int32_t* first_hit, float* ap, const int64_t* topk, int ntopk, float* cmc, void* stream);
 
+/* Matrix-free rank metrics (evaluation.py:11-37 rank / mAP, :40-65 k-reciprocal re-rank, :144-163 the four tables): CMC and
+ * mAP from the RANK of every relevant gallery row, r(q,j) = 1 + #{i : s(q,i) > s(q,j) or (s(q,i) == s(q,j) and i < j)} - the
+ * order of trid_argsort_rows_desc_f32 - without the [Q,G] similarity and index matrices.  The relevant pairs are a CSR list:
+ * ptr [Q+1] i64, idx [NP] i64 = row of each pair within the g passed, ascending per query.  Two sub-passes share one tile code,
+ * so a row compares equal to its own duplicate:
+ *   mode 0 (pair values): val[e] = s(q(e), idx[e]);
+ *   mode 1 (count): counts[e] += #{rows of g preceding pair e}, thresholds read from val; counts is zeroed by the caller,
+ *     merged by integer atomics (run-to-run identical); max_list = the longest list of a query (a host value: the gallery
+ *     streams once per 6 entries of it).  Nothing is stored per element.
+ * offset: global index of g's row 0 (as trid_sim_topk_*).  CURRENTLY UNUSED beyond its check (>= 0): the listed rows and the
+ * streamed rows belong to the same g, so the tie-break on offset + i is the local order i < j and the kernels compare local
+ * rows.  It is the argument the sharded form (thresholds all-gathered with GLOBAL rows, counts summed) will compare against.
+ * Limits: a list passed to mode 0 of trid_rank_stream_p16 holds fewer than 2^21 pairs (the gathered rows stay below 2 GB;
+ * the Python host chunks longer lists); trid_rank_stream_f32 needs the whole [Q, 8192] panel, it does not chunk over Q.
+ * trid_rank_stream_p16: C == 256, operands pre-split (q16 = P16 [ceil32(Q)][256], padding rows zero; trid_p16_pack_f32) on the
+ * streaming kernel with the queries resident in registers (csrc/gemm_stream.hip); mode 0 streams the GATHERED rows of the
+ * list (a16 = g16[idx], G == NP), mode 1 the gallery (a16 = g16).  trid_rank_stream_f32: any C % 4 == 0 and precision, from
+ * the [Q, 8192] panel GEMM, one panel at a time; ws floats >= trid_rank_ws_floats(Q, G). */
+long long trid_rank_ws_floats(int Q, int G);
+int trid_rank_stream_p16(const void* q16, const void* a16, const float* q_amax, const float* g_amax, const int64_t* ptr,
+                         const int64_t* idx, float* val, int32_t* counts, int Q, int G, long long NP, int max_list,
+                         long long offset, int mode, void* stream);
+int trid_rank_stream_f32(const float* q, const float* g, const int64_t* ptr, const int64_t* idx, float* val, int32_t* counts,
+                         int Q, int G, int C, long long NP, int max_list, long long offset, int precision, const float* q_amax,
+                         const float* g_amax, float* ws, int mode, void* stream);
+/* Re-rank (evaluation.py:40-65, 144-163): s'(q,i) = s(q,i) + alpha*jaccard(qnn[q,:n], gnn[i,:n]), n <= 8, differs from s only
+ * where the neighbour sets intersect.  trid_rank_pairs_jaccard_f32 adds the term to the values of a pair list (the thresholds);
+ * the count pass then runs on the plain similarities, and trid_rank_rerank_fix corrects counts over the list nb_* of ALL pairs
+ * with intersecting neighbour sets (nb_val = their plain values, mode 0 above): each takes back its plain vote and casts the
+ * re-ranked one. */
+int trid_rank_pairs_jaccard_f32(const int64_t* ptr, const int64_t* idx, float* val, const int64_t* qnn, const int64_t* gnn,
+                                int n, float alpha, int Q, long long NP, void* stream);
+int trid_rank_rerank_fix(const int64_t* pos_ptr, const int64_t* pos_idx, const float* thr, int32_t* counts, const int64_t* nb_ptr,
+                         const int64_t* nb_idx, const float* nb_val, const int64_t* qnn, const int64_t* gnn, int n, float alpha,
+                         int Q, long long NB, void* stream);
+/* counts [NP] (= rank - 1) -> first_hit[q] = the smallest (INT_MAX without relevant rows), ap[q] = (1/P) sum_k k / r_(k) over the
+ * query's ranks in ascending order (NaN when P == 0), cmc[t] = 100*mean(first_hit < topk[t]), any topk (evaluation.py:20-36) */
+int trid_rank_finalize(const int32_t* counts, const int64_t* ptr, int Q, int32_t* first_hit, float* ap, const int64_t* topk,
+                       int ntopk, float* cmc, void* stream);
+
 /* k-reciprocal re-rank term (evaluation.py:40-65): out[i,j] = alpha*jaccard(qnn[i,:k], gnn[j,:k]) + base[i,j]
  * (base may be NULL); qnn [Q,k], gnn [G,k] top-k neighbour indices, k <= 8 */
 int trid_jaccard_add_f32(const int64_t* qnn, const int64_t* gnn, const float* base, long long ldb, float* out, int Q,

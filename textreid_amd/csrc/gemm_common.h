@@ -22,6 +22,19 @@ struct GemmFilter {
     int* overflow;
 };
 
+// Rank-count epilogue of the streaming kernel (gemm_stream.hip FUSE 5, rank_stream.hip): per (query, listed positive)
+// the number of streamed rows that precede the positive in the descending order, ties -> lower row first.  Nothing is
+// stored per element: RANK_PC (threshold, row, counter) triples per query live in LDS for one pass.
+constexpr int RANK_PC = 6;
+struct RankCount {
+    const long long* ptr;  // [Q + 1] CSR over the queries
+    const long long* idx;  // [NP] streamed-row index of each listed pair
+    float* val;            // [NP] pair_mode: written (the pair's own value); else read (thresholds)
+    int* counts;           // [NP] += (integer atomics)
+    int p0;                // this pass counts entries p0 .. p0 + RANK_PC - 1 of every query's list
+    int pair_mode;         // 1: the streamed rows ARE the listed rows, gathered in CSR order; row r's value goes to val[r]
+};
+
 // Eval-mode epilogues (BatchNorm of running statistics, ReLU, residual fused into the convolution: m_resnet.py:54-67 under
 // model.eval()) write their output as a P16 tensor, so its fp16 scale must be fixed before the first element is known.
 // It comes from a BOUND that needs no pass over anything:
@@ -116,6 +129,9 @@ namespace trid {
 // retrieval (gemm_stream.hip): the admission-filter pass on pre-split operands, queries resident in registers
 int stream_topk_filter(const void* g16, const float* g_amax, const void* q16, const float* q_amax, int G, int Q, const GemmFilter& filt,
                        hipStream_t stream);
+// ... the same pass structure with the rank-count epilogue: a16 = P16 [M][256] (the gallery, or the gathered rows of rk.idx)
+int stream_rank_count(const void* a16, const float* a_amax, const void* q16, const float* q_amax, int M, int Q, const RankCount& rk,
+                      hipStream_t stream);
 }  // namespace trid
 
 // trid_gemm_f32 plus the internal extras (either may be null).  With a filter the call returns

@@ -90,6 +90,8 @@ struct StreamParams {
     GemmFilter filt;
     int n_real;              // columns that exist (N is padded to a multiple of 32)
     int flags;               // FUSE == 4: 1 = DMA pieces spread over the k loop, 2 = the upper waves scan one step late
+    // FUSE == 5 (rank metrics, stream_rank_count): the loop of FUSE == 4 with counters in place of the candidate lists
+    RankCount rk;
 };
 
 __device__ __forceinline__ void lds_store1(const void* p, float v) {
@@ -129,6 +131,10 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
     // FUSE == 3: the statistics-only pass (nothing is stored but the partials).  Without the output stream a step is over in
     // a fraction of the HBM latency, so one tile in flight per workgroup starves it (66 us for 100 MB): THREE stages, two
     // tiles in flight.  (With C stores in between the 6-bit in-order vmcnt could not tell the older DMA from the newer one.)
+    // FUSE == 5: the rank-count pass of the matrix-free mAP (evaluation.py:11-37): the same resident queries and gallery stream;
+    // a lane keeps RANK_PC (threshold, row, counter) triples of its query and counts the elements that precede each listed
+    // positive - or, in pair mode, stores the value of the pairs the CSR list names and nothing else
+    constexpr bool RETR = FUSE == 4 || FUSE == 5;  // the retrieval loop: DMA spread over the k loop, late scan of the upper waves
     constexpr int NS = FUSE == 3 ? 3 : 2;
     constexpr int NW = 8, RW = NW / CW;
     constexpr int RB = RW * TM * 32;          // rows per step
@@ -180,6 +186,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(p.stats != nullptr ? p.stats : p.C), 0, (unsigned)((size_t)p.tiles * p.N * 16), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc((void*)(p.cmask != nullptr ? (const void*)p.cmask : (const void*)p.C), 0, (unsigned)((size_t)p.M * p.N / 8), 0x00020000);
     constexpr unsigned OOB = 0x80000000u;
+    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)(FUSE == 5 ? (void*)p.rk.val : (void*)p.C), 0, (unsigned)((size_t)p.M * 4), 0x00020000);
 
     // FUSE: this lane's 8 channels (octet oc of the wave's 32 columns; the same in both halves of a tile) and their coefficients
     constexpr bool FEPI = FUSE == 1 || FUSE == 2;
@@ -211,6 +218,38 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
     if constexpr (FUSE == 4) {
         const int col = n0 + (lane & 31);
         if (col_live && col < p.n_real) f_thr = p.filt.thr[(long long)col * p.filt.thr_stride];
+    }
+    // FUSE == 5: this lane's query: its CSR range and RANK_PC counters.  The (threshold, row) pairs they count against wait in
+    // a wave-private LDS table ([32 queries][RANK_PC thresholds | RANK_PC rows], empty slots +inf / -1) and come into registers
+    // only for a step that has an element above the query's lowest threshold: held across the k loop beside the 128-VGPR
+    // query panel they spilled
+    constexpr int RPCN = FUSE == 5 ? RANK_PC : 1;
+    int r_lo = 0, r_hi = 0;
+    unsigned r_lds = 0, r_cnt = 0;  // LDS byte addresses: the query's (threshold, row) table, this lane's counters
+    if constexpr (FUSE == 5) {
+        float* const rtab = reinterpret_cast<float*>(sstat);  // (right behind the ring: [NW] tables, [NW] x 64 lanes of counters)
+        const int col = n0 + (lane & 31);
+        if (col_live && col < p.n_real) {
+            r_lo = (int)p.rk.ptr[col];
+            r_hi = (int)p.rk.ptr[col + 1];
+        }
+        r_lds = (unsigned)(uintptr_t)(rtab + wave * (64 * RPCN)) + (unsigned)(lane & 31) * (8u * RPCN);
+        r_cnt = (unsigned)(uintptr_t)(rtab + NW * (64 * RPCN) + wave * (64 * RPCN)) + (unsigned)lane * (4u * RPCN);
+        asm volatile("" : "+v"(r_lds), "+v"(r_cnt));
+#pragma unroll
+        for (int u = 0; u < RPCN; ++u) {
+            const int e = r_lo + p.rk.p0 + u;
+            const bool ok = !p.rk.pair_mode && e < r_hi;
+            const float tu = ok ? p.rk.val[e] : INFINITY;
+            const int ju = ok ? (int)p.rk.idx[e] : -1;
+            if (khalf == 0) {
+                lds_store1u(r_lds + 4u * u, __float_as_uint(tu));
+                lds_store1u(r_lds + 4u * (RPCN + u), (unsigned)ju);
+            }
+            lds_store1u(r_cnt + 4u * u, 0u);
+            f_thr = fminf(f_thr, tu);  // (the query's lowest threshold of this pass: the wave-uniform early-out)
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     // FUSE == 4: this wave's staging list of candidates, [FCAP] x (value, gallery row, query), and its counter
     constexpr int FCAP = 128;
@@ -268,7 +307,61 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
     // FUSE == 4: the waves of one SIMD (w and w + 4) leave every barrier together and would issue their DMA, run their MFMAs and
     // scan their accumulators in phase - the matrix pipe idle while both do something else.  The upper four waves therefore
     // scan the accumulators of step t AFTER the barrier of step t + 1, under the MFMAs of the lower four
-    const bool late = FUSE == 4 && (p.flags & 2) != 0 && wave >= 4;
+    const bool late = RETR && (p.flags & 2) != 0 && wave >= 4;
+    auto rank_epi = [&](int tt) {
+        if constexpr (FUSE == 5) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][r] *= unscale;
+            const int row0 = tt * RB + rw * TM * 32;  // (M * 1024 < 2^31: rows fit an int)
+            const int rb = row0 + 4 * khalf;
+            if (p.rk.pair_mode) {
+                // rows r_lo .. r_hi - 1 of the stream are this query's pairs: their values are the only output
+                if (__ballot(r_lo < row0 + TM * 32 && r_hi > row0) == 0ull) return;
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rb + i * 32 + (r & 3) + 8 * (r >> 2);
+                        // (32-bit offsets into the descriptor of val; a row of another query goes out of range: dropped)
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[i][r]), rsV, (row >= r_lo && row < r_hi) ? (unsigned)row * 4u : OOB, 0, 0);
+                    }
+                return;
+            }
+            if ((long long)(tt + 1) * RB > p.M) {  // (a ragged last tile read zeros)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (rb + i * 32 + (r & 3) + 8 * (r >> 2) >= p.M) acc[i][r] = -INFINITY;
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[i][r]);
+            if (__ballot(mx >= f_thr) == 0ull) return;
+            // one listed positive at a time (three registers: threshold, row, count); its counter is this lane's word of the
+            // wave's LDS table
+#pragma unroll 1
+            for (int u = 0; u < RPCN; ++u) {
+                const float tu = __uint_as_float(lds_load1(r_lds + 4u * u));
+                const int ju = (int)lds_load1(r_lds + 4u * (RPCN + u));
+                if (__ballot(mx >= tu) == 0ull) continue;
+                int c = 0;
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = acc[i][r];
+                        const int row = rb + i * 32 + (r & 3) + 8 * (r >> 2);
+                        c += (v > tu || (v == tu && row < ju)) ? 1 : 0;
+                    }
+                if (c != 0) lds_store1u(r_cnt + 4u * u, lds_load1(r_cnt + 4u * u) + (unsigned)c);
+            }
+        }
+    };
     auto filter_epi = [&](int tt) {
         if constexpr (FUSE == 4) {
 #pragma unroll
@@ -336,7 +429,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
 #pragma unroll
         for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(fsc[j]), "+v"(fsh[j]));
     }
-    if constexpr (FUSE == 4) asm volatile("" : "+v"(f_thr));
+    if constexpr (RETR) asm volatile("" : "+v"(f_thr));
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt untouched
     int t = worker;
     if (t < p.tiles) issue(t, 0, 0);
@@ -359,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
             } else {
                 wait_vm<0>();
             }
-        } else if constexpr (FUSE == 4) {
+        } else if constexpr (RETR) {
             wait_vm<0>();  // (the only vector-memory traffic besides this tile's DMA: the rare candidate appends of the last step)
         } else {
             if (first) wait_vm<0>();
@@ -369,6 +462,9 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         lds_barrier();
         if constexpr (FUSE == 4) {
             if (late && !first) filter_epi(t - p.workers);
+        }
+        if constexpr (FUSE == 5) {
+            if (late && !first) rank_epi(t - p.workers);
         }
         const int tn = t + (NS - 1) * p.workers;
         // RW > 1: the previous step's BatchNorm partials, merged by the first lanes of the workgroup (one column each)
@@ -442,7 +538,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         }
         int zero = 0;
         asm volatile("" : "+v"(zero));
-        const bool dma_spread = FUSE == 4 && (p.flags & 1) != 0;  // the DMA pieces among the MFMAs instead of ahead of them
+        const bool dma_spread = RETR && (p.flags & 1) != 0;  // the DMA pieces among the MFMAs instead of ahead of them
         if (tn < p.tiles && !dma_spread) issue(tn, NS == 2 ? (stage ^ 1) : (stage == 0 ? NS - 1 : stage - 1), zero);
 
         // ---- MFMAs of this tile: per 16-deep k step 2 fragment reads per row block, 3 products
@@ -453,7 +549,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         const char* sA = ring + stage * STAGE;
         // fragment prefetch distance: 1 k step (two register sets).  (The retrieval filter runs two waves per SIMD - its 128-VGPR
         // query panel - at 44 % MFMA-busy; a distance of 2 (three sets, 256 VGPRs) measured the same 16.4 ms: TRID_TOPK_PF)
-        constexpr int PF = FUSE == 4 ? TRID_TOPK_PF : 1;
+        constexpr int PF = RETR ? TRID_TOPK_PF : 1;
         f16x8 af[PF + 1][TM][2];
         auto fetch = [&](int q, f16x8(&dst)[TM][2]) {  // q = k group * 2 + k step
             const int g = q >> 1, ks = q & 1;
@@ -469,7 +565,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
 #pragma unroll
         for (int q = 0; q < 2 * KG; ++q) {
             if (q + PF < 2 * KG) fetch(q + PF, af[(q + PF) % (PF + 1)]);
-            if constexpr (FUSE == 4) {
+            if constexpr (RETR) {
                 if (dma_spread && tn < p.tiles && (q & 1) == 0 && (q >> 1) < DPW) issue_piece(tn, stage ^ 1, zero, q >> 1);
             }
             const int g = q >> 1, ks = q & 1;
@@ -483,7 +579,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         }
 
         // ---- epilogue
-        if constexpr (FUSE != 4) {
+        if constexpr (!RETR) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -568,7 +664,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
             // (no C - the statistics-only pass: every store is out of range, the instruction count the waits rely on stays)
             const unsigned ldcb = (unsigned)p.ldc * 4u;
             const unsigned base = (col_live && p.C != nullptr) ? (unsigned)row0 * ldcb + 4u * khalf * ldcb + (unsigned)(n0 + (lane & 31)) * 4u : OOB;
-            if constexpr (FUSE != 1 && FUSE != 3 && FUSE != 4) {
+            if constexpr (FUSE != 1 && FUSE != 3 && !RETR) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -580,6 +676,9 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         }
         if constexpr (FUSE == 4) {
             if (!late) filter_epi(t);
+        }
+        if constexpr (FUSE == 5) {
+            if (!late) rank_epi(t);
         }
         if constexpr (FUSE == 1 || FUSE == 2) {
             // out = relu(y * scale + shift + identity) as a P16 tensor, the arithmetic of bn_apply_kernel<1, 1> (bn_pool.hip).
@@ -685,6 +784,18 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
         if (late && !first) filter_epi(t - p.workers);
         const unsigned staged = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_load1(f_wcnt));
         if (staged != 0u) flush_staged(staged);
+    }
+    if constexpr (FUSE == 5) {
+        if (late && !first) rank_epi(t - p.workers);
+        if (!p.rk.pair_mode) {
+            // the two lanes of a query (k halves: rows 4 apart) hold partial counts; workgroups merge by INTEGER atomics
+#pragma unroll
+            for (int u = 0; u < RPCN; ++u) {
+                const int cl = (int)lds_load1(r_cnt + 4u * u);
+                const int c = cl + __shfl_xor(cl, 32, 64);
+                if (khalf == 0 && r_lo + p.rk.p0 + u < r_hi && c != 0) atomicAdd(p.rk.counts + r_lo + p.rk.p0 + u, c);
+            }
+        }
     }
     if constexpr (FUSE == 1 || FUSE == 2) {
         if (p.ev.out_tmax != nullptr) {  // one atomic per workgroup
@@ -828,28 +939,21 @@ extern "C" int trid_gemm_p16_stream(const void* A, const float* a_amax, const vo
 // [G][256]): every similarity >= thr[query * thr_stride] is appended to the query's list (value, gallery row + col0).
 // 1280 persistent workgroups = 5 full rounds of the chip for Q = 1e4 (40 query panels x 32 workers; the panels of one worker
 // index share an XCD and walk the same gallery tiles: the gallery crosses the fabric once per XCD, not once per panel).
-int trid::stream_topk_filter(const void* g16, const float* g_amax, const void* q16, const float* q_amax, int G, int Q, const GemmFilter& filt,
-                             hipStream_t stream) {
-    const int Qp = (Q + 31) / 32 * 32;
-    TRID_REQUIRE(g16 && q16 && g_amax && q_amax && G > 0 && Q > 0 && filt.thr && filt.cnt && filt.cand && filt.overflow, "stream_topk_filter: null operand");
-    TRID_REQUIRE(aligned16(g16) && aligned16(q16) && (long long)G * 1024 < (1ll << 31), "stream_topk_filter: 16-byte aligned operands, gallery shard below 2 GB");
-    StreamParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const char*)g16; p.B = (const char*)q16; p.C = nullptr;
-    p.a_amax = g_amax; p.b_amax = q_amax;
-    p.M = G; p.N = Qp; p.ldc = Qp;
-    p.filt = filt; p.n_real = Q;
+template <int FUSE>
+static int launch_retrieval(StreamParams& p, const char* what, hipStream_t stream) {
+    const int G = p.M, Qp = p.N;
     static const int f_env = getenv("TRID_TOPK_FLAGS") ? atoi(getenv("TRID_TOPK_FLAGS")) : 3;  // (A/B runs: tools/exp/r05_run9.sh)
     p.flags = f_env;
     constexpr int K = 256, CW = 8, TM = 2, RB = TM * 32;
-    const size_t lds = (size_t)2 * RB * K * 4 + 2 * 8 * 32 * sizeof(float4) + (size_t)8 * 3 * 128 * 4;  // ring, counters, staging lists
+    // ring, counters, staging lists (FUSE 5: the threshold tables)
+    const size_t lds = (size_t)2 * RB * K * 4 + 2 * 8 * 32 * sizeof(float4) + (FUSE == 5 ? (size_t)2 * 8 * 64 * RANK_PC * 4 - 2 * 8 * 32 * sizeof(float4) : (size_t)8 * 3 * 128 * 4);
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)gemm_p16_stream_kernel<K, CW, TM, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_err = hipFuncSetAttribute((const void*)gemm_p16_stream_kernel<K, CW, TM, false, FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     if (attr_err != hipSuccess) {
-        set_error("stream_topk_filter: cannot reserve LDS: %s", hipGetErrorString(attr_err));
+        set_error("%s: cannot reserve LDS: %s", what, hipGetErrorString(attr_err));
         return (int)attr_err;
     }
     p.panels = (Qp + CW * 32 - 1) / (CW * 32);
@@ -868,8 +972,38 @@ int trid::stream_topk_filter(const void* g16, const float* g_amax, const void* q
     static const int w_env = getenv("TRID_TOPK_WORKERS") ? atoi(getenv("TRID_TOPK_WORKERS")) : 0;  // (experiments)
     if (w_env > 0) workers = w_env;
     p.workers = std::min(workers, (p.tiles + 7) / 8 * 8);
-    hipLaunchKernelGGL((gemm_p16_stream_kernel<K, CW, TM, false, 4>), dim3(p.workers * p.panels), dim3(512), lds, stream, p);
-    return check_launch("stream_topk_filter");
+    hipLaunchKernelGGL((gemm_p16_stream_kernel<K, CW, TM, false, FUSE>), dim3(p.workers * p.panels), dim3(512), lds, stream, p);
+    return check_launch(what);
+}
+
+int trid::stream_topk_filter(const void* g16, const float* g_amax, const void* q16, const float* q_amax, int G, int Q, const GemmFilter& filt,
+                             hipStream_t stream) {
+    const int Qp = (Q + 31) / 32 * 32;
+    TRID_REQUIRE(g16 && q16 && g_amax && q_amax && G > 0 && Q > 0 && filt.thr && filt.cnt && filt.cand && filt.overflow, "stream_topk_filter: null operand");
+    TRID_REQUIRE(aligned16(g16) && aligned16(q16) && (long long)G * 1024 < (1ll << 31), "stream_topk_filter: 16-byte aligned operands, gallery shard below 2 GB");
+    StreamParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = (const char*)g16; p.B = (const char*)q16; p.C = nullptr;
+    p.a_amax = g_amax; p.b_amax = q_amax;
+    p.M = G; p.N = Qp; p.ldc = Qp;
+    p.filt = filt; p.n_real = Q;
+    return launch_retrieval<4>(p, "stream_topk_filter", stream);
+}
+
+// Rank metrics: the same launch with the counting epilogue (FUSE 5).  a16: the rows that stream - the gallery (count mode) or
+// the gathered rows of the CSR list (pair mode)
+int trid::stream_rank_count(const void* a16, const float* a_amax, const void* q16, const float* q_amax, int M, int Q, const RankCount& rk,
+                            hipStream_t stream) {
+    const int Qp = (Q + 31) / 32 * 32;
+    TRID_REQUIRE(a16 && q16 && a_amax && q_amax && M > 0 && Q > 0 && rk.ptr && rk.idx && rk.val && (rk.pair_mode || rk.counts), "stream_rank_count: null operand");
+    TRID_REQUIRE(aligned16(a16) && aligned16(q16) && (long long)M * 1024 < (1ll << 31), "stream_rank_count: 16-byte aligned operands, streamed rows below 2 GB");
+    StreamParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = (const char*)a16; p.B = (const char*)q16; p.C = nullptr;
+    p.a_amax = a_amax; p.b_amax = q_amax;
+    p.M = M; p.N = Qp; p.ldc = Qp;
+    p.rk = rk; p.n_real = Q;
+    return launch_retrieval<5>(p, "stream_rank_count", stream);
 }
 
 // shapes the fused conv3 + BatchNorm + identity + ReLU kernel covers (K = planes of layer1 - layer3, N = 4 planes)

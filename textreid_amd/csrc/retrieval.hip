@@ -225,6 +225,35 @@ __global__ __launch_bounds__(256) void cmc_kernel(const int32_t* __restrict__ fi
     }
 }
 
+// One wave per query: its P counts (= rank - 1, all different) are ordered by enumeration - the k-th smallest is the one with
+// k - 1 smaller ones - and AP = (1/P) sum k / rank; first_hit = the smallest count (INT_MAX without positives, AP NaN then)
+__global__ __launch_bounds__(256) void rank_finalize_kernel(const int* __restrict__ counts, const long long* __restrict__ ptr, int Q,
+                                                            int32_t* __restrict__ first_hit, float* __restrict__ ap) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) return;
+    const long long b = ptr[q], e = ptr[q + 1];
+    double acc = 0.0;
+    int first = 0x7fffffff;
+    for (long long p = b + lane; p < e; p += 64) {
+        const int c = counts[p];
+        int k = 1;
+        for (long long o = b; o < e; ++o) k += counts[o] < c ? 1 : 0;
+        acc += (double)k / (double)(c + 1);
+        first = c < first ? c : first;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_xor(acc, o, 64);
+        const int f = __shfl_xor(first, o, 64);
+        first = f < first ? f : first;
+    }
+    if (lane == 0) {
+        first_hit[q] = first;
+        ap[q] = (float)acc / (float)(e - b);  // NaN when the query has no relevant gallery item, as the reference
+    }
+}
+
 // k-reciprocal re-rank term (evaluation.py:40-65): out[i,j] = alpha * |A_i n B_j| / |A_i u B_j| (+ base[i,j])
 // for the top-k neighbour index sets A_i = qnn[i,:], B_j = gnn[j,:] (k <= 8, indices unique per row).
 __global__ __launch_bounds__(256) void jaccard_add_kernel(const long long* __restrict__ qnn,
@@ -483,4 +512,13 @@ extern "C" int trid_jaccard_add_f32(const int64_t* qnn, const int64_t* gnn, cons
     hipLaunchKernelGGL(jaccard_add_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)qnn,
                        (const long long*)gnn, base, ldb, out, Q, G, k, alpha);
     return check_launch("trid_jaccard_add_f32");
+}
+
+// matrix-free rank metrics (rank_stream.hip): counts [NP] = rank - 1 of every listed positive, CSR over the queries
+extern "C" int trid_rank_finalize(const int32_t* counts, const int64_t* ptr, int Q, int32_t* first_hit, float* ap, const int64_t* topk,
+                                  int ntopk, float* cmc, void* stream) {
+    TRID_REQUIRE(ptr && first_hit && ap && topk && cmc && Q > 0 && ntopk > 0, "trid_rank_finalize: bad arguments");
+    hipLaunchKernelGGL(rank_finalize_kernel, dim3((Q + 3) / 4), dim3(256), 0, (hipStream_t)stream, counts, (const long long*)ptr, Q, first_hit, ap);
+    hipLaunchKernelGGL(cmc_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, first_hit, Q, topk, ntopk, cmc);
+    return check_launch("trid_rank_finalize");
 }

@@ -171,6 +171,214 @@ def k_reciprocal(q_feats, g_feats, neighbor_num=5, alpha=0.05, base=None):
     return out
 
 
+def _refuse(name, *tensors):
+    from .parallel import dp_active
+
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("textreid_amd.evaluation.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
+    if dp_active():
+        raise NotImplementedError("textreid_amd.evaluation.%s: the sharded form (all-gather of the thresholds, SUM-reduce of the "
+                                  "counts over the gallery shards) is not built; run it on one rank" % name)
+    if torch.cuda.is_current_stream_capturing():
+        # the CSR lists' lengths and the longest list are host values (one pass of the gallery per RANK_PC entries of it)
+        raise RuntimeError("textreid_amd.evaluation.%s reads list lengths back to the host and cannot run inside a stream capture" % name)
+
+
+def _expand_ranges(lo, cnt):
+    """entries lo[r] .. lo[r] + cnt[r] - 1 of every range r, concatenated: (range id, entry) - device bookkeeping, no host loop"""
+    rid = torch.repeat_interleave(torch.arange(cnt.numel(), device=cnt.device), cnt)
+    first = torch.cumsum(cnt, 0) - cnt
+    return rid, lo[rid] + (torch.arange(rid.numel(), device=cnt.device) - first[rid])
+
+
+def _csr(qid, idx, Q, G):
+    """unique (query, row) pairs in (query, row) order -> (ptr [Q+1], idx) int64"""
+    key = torch.unique(qid * G + idx)  # sorted
+    ptr = torch.searchsorted(key, torch.arange(Q + 1, device=key.device) * G)
+    return ptr.contiguous(), (key % G).contiguous()
+
+
+def _positive_list(q_pids, g_pids):
+    """CSR list of the gallery rows that carry each query's pid, rows ascending"""
+    dev = g_pids.device
+    gp, order = torch.sort(g_pids.long())
+    qp = q_pids.to(dev).long()
+    lo = torch.searchsorted(gp, qp)
+    rid, ent = _expand_ranges(lo, torch.searchsorted(gp, qp, right=True) - lo)
+    return _csr(rid, order[ent], qp.numel(), gp.numel())
+
+
+def _neighbour_list(qnn, gnn):
+    """CSR list of ALL pairs (q, i) whose neighbour rows share an index: the only ones the Jaccard term moves"""
+    Q, n = qnn.shape
+    G = gnn.shape[0]
+    vals, order = torch.sort(gnn.reshape(-1))
+    flat = qnn.reshape(-1)
+    lo = torch.searchsorted(vals, flat)
+    rid, ent = _expand_ranges(lo, torch.searchsorted(vals, flat, right=True) - lo)
+    return _csr(rid // n, order[ent] // n, Q, G)
+
+
+PAIR_CHUNK = 1 << 18  # listed pairs per pair-value launch of the streaming kernel (256 MB of gathered gallery rows)
+
+
+class _RankOperands:
+    """q and g as the rank passes take them: pre-split once for the streaming kernel (the case _sim_topk_call runs on it), else
+    the fp32 rows and ONE [Q, 8192] panel."""
+
+    def __init__(self, q, g):
+        self.q, self.g = q, g
+        self.Q, self.C = q.shape
+        self.G = g.shape[0]
+        self.prec, self.qa, self.ga = _sim_precision(q, g)
+        self.p16 = USE_SIM_P16 and self.prec == 16 and self.C == 256 and self.G > 8192 and self.G * 1024 < (1 << 31)
+        if self.p16:
+            self.q16 = torch.zeros((self.Q + 31) // 32 * 32, self.C, dtype=torch.float32, device=q.device)
+            call("trid_p16_pack_f32", _p(q), self.Q, self.C, self.C, _p(self.qa), _p(self.q16), 1, stream())
+            self.g16 = torch.empty_like(g)
+            call("trid_p16_pack_f32", _p(g), self.G, self.C, self.C, _p(self.ga), _p(self.g16), 1, stream())
+        else:
+            self.ws = ops.empty((ops.L.load().trid_rank_ws_floats(self.Q, self.G),), q)
+
+    def run(self, ptr, idx, val, counts, max_list, mode):
+        NP = idx.numel()
+        if NP == 0:
+            return
+        if self.p16 and mode == 0:
+            # pair values: the listed rows are gathered and stream through the counting tile code, PAIR_CHUNK entries at a time
+            # (the gathered copy stays small; the kernel's 31-bit offsets allow 2^21 rows): entries a .. b - 1 with the CSR
+            # ranges cut to them
+            for a in range(0, NP, PAIR_CHUNK):
+                b = min(a + PAIR_CHUNK, NP)
+                cptr = (ptr.clamp(a, b) - a).contiguous()
+                cidx, cval, a16 = idx[a:b], val[a:b], self.g16[idx[a:b]]
+                call("trid_rank_stream_p16", _p(self.q16), _p(a16), _p(self.qa), _p(self.ga), _p(cptr), _p(cidx), _p(cval), None, self.Q,
+                     b - a, b - a, 0, 0, 0, stream())
+        elif self.p16:
+            call("trid_rank_stream_p16", _p(self.q16), _p(self.g16), _p(self.qa), _p(self.ga), _p(ptr), _p(idx), _p(val), _p(counts), self.Q,
+                 self.G, NP, max_list, 0, 1, stream())
+        else:
+            call("trid_rank_stream_f32", _p(self.q), _p(self.g), _p(ptr), _p(idx), _p(val), _p(counts), self.Q, self.G, self.C, NP, max_list,
+                 0, self.prec, _p(self.qa), _p(self.ga), _p(self.ws), mode, stream())
+
+
+def _positive_counts(q, g, q_pids, g_pids, qnn, gnn, alpha):
+    dev = q.device
+    Q, G = q.shape[0], g.shape[0]
+    ptr, idx = _positive_list(q_pids, g_pids.to(dev))
+    NP = idx.numel()
+    counts = torch.zeros(max(NP, 1), dtype=torch.int32, device=dev)
+    thr = torch.empty(max(NP, 1), dtype=torch.float32, device=dev)
+    if NP == 0:
+        return ptr, idx, counts[:0], thr[:0]
+    opnd = _RankOperands(q, g)
+    max_list = int((ptr[1:] - ptr[:-1]).max())
+    opnd.run(ptr, idx, thr, None, 0, 0)
+    if qnn is not None:
+        n = qnn.shape[1]
+        qnn, gnn = qnn.long().contiguous(), gnn.long().contiguous()
+        call("trid_rank_pairs_jaccard_f32", _p(ptr), _p(idx), _p(thr), _p(qnn), _p(gnn), n, float(alpha), Q, NP, stream())
+    opnd.run(ptr, idx, thr, counts, max_list, 1)
+    if qnn is not None:
+        nb_ptr, nb_idx = _neighbour_list(qnn, gnn)
+        NB = nb_idx.numel()
+        if NB:
+            nb_val = torch.empty(NB, dtype=torch.float32, device=dev)
+            opnd.run(nb_ptr, nb_idx, nb_val, None, 0, 0)
+            call("trid_rank_rerank_fix", _p(ptr), _p(idx), _p(thr), _p(counts), _p(nb_ptr), _p(nb_idx), _p(nb_val), _p(qnn), _p(gnn), n,
+                 float(alpha), Q, NB, stream())
+    return ptr, idx, counts, thr
+
+
+def positive_ranks(q, g, q_pids, g_pids, qnn=None, gnn=None, alpha=0.05, normalize=False):
+    """Overall rank (1-based, int64, CSR order) of every relevant gallery row of every query under s'(q,i) = q_i . g_i +
+    alpha * Jaccard(qnn[q], gnn[i]) (no neighbours: the plain similarity), descending, ties lower index first - what a full
+    argsort of the [Q,G] matrix would give (evaluation.py:14), without the matrix.  -> (pos_ptr [Q+1], pos_idx [NP], ranks [NP])"""
+    _refuse("positive_ranks", q, g)
+    if (qnn is None) != (gnn is None):
+        raise ValueError("positive_ranks: qnn and gnn go together")
+    q = l2_normalize_rows(q) if normalize else q.contiguous().float()
+    g = l2_normalize_rows(g) if normalize else g.contiguous().float()
+    ptr, idx, counts, _ = _positive_counts(q, g, q_pids, g_pids, qnn, gnn, alpha)
+    return ptr, idx, counts.long() + 1
+
+
+def rank_from_embeddings(text_embed, image_embed, q_pids, g_pids, topk=(1, 5, 10), get_mAP=True, normalize=True, rerank=False,
+                         neighbor_num=5, alpha=0.05):
+    """rank() (evaluation.py:11-37) from the embeddings: CMC at any k and mAP from the ranks of the relevant rows; with rerank the
+    k-reciprocal term (evaluation.py:40-65) is part of the compared value.  No [Q,G] tensor.  -> (cmc, mAP) or (cmc,)"""
+    _refuse("rank_from_embeddings", text_embed, image_embed)
+    dev = text_embed.device
+    q = l2_normalize_rows(text_embed) if normalize else text_embed.contiguous().float()
+    g = l2_normalize_rows(image_embed) if normalize else image_embed.contiguous().float()
+    qnn = gnn = None
+    if rerank:
+        qnn = _topk_neighbours(q, g, neighbor_num)
+        gnn = _topk_neighbours(g, g, neighbor_num)
+    ptr, idx, counts, _ = _positive_counts(q, g, q_pids, g_pids, qnn, gnn, alpha)
+    Q = q.shape[0]
+    topk_t = torch.as_tensor(topk, dtype=torch.int64, device=dev)
+    first = torch.empty(Q, dtype=torch.int32, device=dev)
+    ap = torch.empty(Q, dtype=torch.float32, device=dev)
+    cmc = torch.empty(topk_t.numel(), dtype=torch.float32, device=dev)
+    call("trid_rank_finalize", _p(counts), _p(ptr), Q, _p(first), _p(ap), _p(topk_t), topk_t.numel(), _p(cmc), stream())
+    if not get_mAP:
+        return (cmc,)
+    mAP = torch.empty(1, dtype=torch.float32, device=dev)
+    ops.sum_to(ap, mAP, 100.0 / Q)
+    return cmc, mAP[0]
+
+
+def _evaluation_matrix_free(dataset, predictions, output_folder, topk, save_data, rerank, logger):
+    embed_dir = os.path.join(output_folder, "inference_embed.npz") if output_folder else None
+    if predictions is None:
+        data = np.load(embed_dir)
+        logger.info("Load inference embeddings from %s", embed_dir)
+        dev = torch.device("cuda")
+        image_pid = torch.as_tensor(data["image_pid"]).to(dev)
+        text_pid = torch.as_tensor(data["text_pid"]).to(dev)
+        image_global = torch.as_tensor(data["image_embed"]).float().to(dev).contiguous()
+        text_global = torch.as_tensor(data["text_embed"]).float().to(dev).contiguous()
+    else:
+        image_ids, pids, image_global, text_global = [], [], [], []
+        for idx, prediction in predictions.items():
+            image_id, pid = dataset.get_id_info(idx)
+            image_ids.append(image_id)
+            pids.append(pid)
+            image_global.append(prediction[0])
+            text_global.append(prediction[1])
+        dev = image_global[0].device
+        image_pid = torch.tensor(pids, device=dev)
+        text_pid = torch.tensor(pids, device=dev)
+        keep = get_unique(image_ids).to(dev)
+        image_global = l2_normalize_rows(torch.stack(image_global, dim=0)[keep])
+        image_pid = image_pid[keep]
+        text_global = l2_normalize_rows(torch.stack(text_global, dim=0))
+        if save_data and embed_dir:
+            np.savez(embed_dir, image_pid=image_pid.cpu().numpy(), text_pid=text_pid.cpu().numpy(),
+                     image_embed=image_global.cpu().numpy(), text_embed=text_global.cpu().numpy())
+    results = {}
+
+    def table(q, g, qp, gp, re):
+        r = rank_from_embeddings(q, g, qp, gp, topk, get_mAP=rerank, normalize=False, rerank=re)
+        return (r[0], r[1] if rerank else None)
+
+    if rerank:
+        results["i2t"] = table(image_global, text_global, image_pid, text_pid, False)
+        results["t2i"] = table(text_global, image_global, text_pid, image_pid, False)
+        results["re-i2t"] = table(image_global, text_global, image_pid, text_pid, True)
+        results["re-t2i"] = table(text_global, image_global, text_pid, image_pid, True)
+        for k, (cmc, mAP) in results.items():
+            logger.info("%-7s topk %s cmc %s mAP %.3f", k, list(topk), [round(float(c), 3) for c in cmc], float(mAP))
+    else:
+        results["t2i"] = table(text_global, image_global, text_pid, image_pid, False)
+        results["i2t"] = table(image_global, text_global, image_pid, text_pid, False)
+        logger.info("topk %s  t2i %s  i2t %s", list(topk), results["t2i"][0].tolist(), results["i2t"][0].tolist())
+    evaluation.last_results = results
+    return results["t2i"][0][0]
+
+
 def get_unique(image_ids):
     keep = {}
     for i, image_id in enumerate(image_ids):
@@ -178,8 +386,12 @@ def get_unique(image_ids):
     return torch.tensor(list(keep.values()))
 
 
-def evaluation(dataset, predictions, output_folder, topk, save_data=True, rerank=True):
+def evaluation(dataset, predictions, output_folder, topk, save_data=True, rerank=True, matrix_free=False):
+    """matrix_free: the four tables from rank_from_embeddings - no [Q,G] tensor is made; save_data then keeps the normalised
+    embeddings and pids (inference_embed.npz), which predictions=None reads back."""
     logger = logging.getLogger("PersonSearch.inference")
+    if matrix_free:
+        return _evaluation_matrix_free(dataset, predictions, output_folder, topk, save_data, rerank, logger)
     data_dir = os.path.join(output_folder, "inference_data.npz") if output_folder else None
     dev = torch.device("cuda")
     rtn = rvn = None
