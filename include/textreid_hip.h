@@ -268,6 +268,34 @@ int trid_subsample2_bwd_f32(const float* g, float* dx, int B, int H, int W, int 
 int trid_global_avgpool_f32(const float* x, float* out, int B, int HW, int C, void* stream);
 int trid_global_avgpool_bwd_f32(const float* g, float* dx, int B, int HW, int C, void* stream);
 
+/* ---- the same encoder under model.eval() on pre-split (P16) activations (csrc/resnet_eval.hip, csrc/gemm_p16.hip): every
+ * convolution one launch whose epilogue applies the running-statistics BatchNorm, clamps and writes the next P16 operand; scale /
+ * maximum scalars as in trid_gemm_desc's eval fields (eval_coef: trid_eval_bound_coefs_f32; out_bound written, out_tmax zeroed by
+ * the caller and atomicMax'ed).
+ * Stem (resnet.py:156-158: relu(bn1(conv1(x))), nn.Conv2d(3, 64, 7, stride=2, padding=3)) straight from the NCHW batch:
+ * out = act(bn_scale[c] * conv1(img) + bn_shift[c]) as a P16 tensor [B][Ho][Wo][64], w [64][147] as stored, eval_tin = max|img|. */
+int trid_stem7_eval_p16(const float* img, const float* w, const float* bn_scale, const float* bn_shift, void* out, const float* eval_coef,
+                        const float* eval_tin, float* out_bound, float* out_tmax, int B, int Hi, int Wi, int relu, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet.py:159) of a P16 tensor x [B][H][W][C] (C % 32 == 0) -> P16
+ * [B][(H-1)/2+1][(W-1)/2+1][C] at the SAME scale (x_amax): the winner's two fp16 parts are copied, so unpack(out) equals the max
+ * pool of unpack(x) exactly; padding is -inf.  out_tmax (may be NULL; zeroed by the caller): the true max|out|. */
+int trid_maxpool3s2_p16(const void* x, const float* x_amax, void* out, float* out_tmax, int B, int H, int W, int C, void* stream);
+/* nn.Conv2d(planes, planes, 3, stride=2, padding=1) + BatchNorm (running statistics) + ReLU (resnet.py:62-70, 85-87 under eval:
+ * layer{2,3,4}.0.conv2) in one launch: x P16 [B][H][W][Cin], w P16 [Cout][9 * Cin] (k = tap * Cin + c) -> out P16
+ * [B][Ho][Wo][Cout], Ho = (H - 1) / 2 + 1 (odd H, W are legal); rows are OUTPUT pixels, tap (ky,kx) reads x[b, 2ho-1+ky, 2wo-1+kx],
+ * zero outside the map (the forward map of trid_gemm_desc.conv_stride == 2 on trid_gemm_p16's LDS-DMA loader and eval epilogue).
+ * Needs Cin % 32 == 0, Cout % 32 == 0, every tensor below 2 GB: trid_conv3x3_s2_eval_p16_ok answers 1. */
+int trid_conv3x3_s2_eval_p16(const void* x, const float* x_amax, const void* w, const float* w_amax, const float* bn_scale,
+                             const float* bn_shift, void* out, const float* eval_coef, const float* eval_tin, float* out_bound,
+                             float* out_tmax, int B, int H, int W, int Cin, int Cout, int relu, void* stream);
+int trid_conv3x3_s2_eval_p16_ok(int B, int H, int W, int Cin, int Cout);
+/* The input of a stride-2 1x1 downsample convolution (resnet.py:137-143) from a P16 tensor: out[b][ho][wo] = x[b][2 ho][2 wo], whole
+ * C * 4-byte rows copied (C % 32 == 0); out is a P16 tensor with x's scale scalar. */
+int trid_subsample2_p16(const void* x, void* out, int B, int H, int W, int C, void* stream);
+/* nn.AdaptiveAvgPool2d((1, 1)) (resnet.py:165) of a P16 tensor x [B][HW][C] (C % 32 == 0): out fp32 [B][C] = mean of the unpacked
+ * values over the HW pixels, summed in pixel order (the arithmetic of trid_global_avgpool_f32). */
+int trid_global_avgpool_p16(const void* x, const float* x_amax, float* out, int B, int HW, int C, void* stream);
+
 /* ---- the stem as bandwidth-shaped kernels (csrc/stem_conv.hip): every input pixel crosses the load path once.
  * Stem conv1 (nn.Conv2d(3, 32, 3, stride=2, padding=1, bias=False), m_resnet.py:161,205) straight from the NCHW image
  * batch [B][3][Hi][Wi] on the exact fp32 MFMA: y [B][Ho][Wo][32] (Ho = ceil(Hi/2), Wo = ceil(Wi/2)), w [32][27] as

@@ -333,6 +333,8 @@ def stem_backward(mod, rec, g, ar, ws, G):
 
 def stem_p16_channels(mod):
     """The P16 stem flow covers the CLIP stem's channel counts: 3 -> 32 -> 32 -> 64."""
+    if not hasattr(mod, "conv3"):  # (the ImageNet ResNet's one-convolution stem: backbones/resnet.py)
+        return False
     return (mod.conv1.in_channels, mod.conv1.out_channels, mod.conv2.out_channels, mod.conv3.out_channels) == (3, 32, 32, 64)
 
 

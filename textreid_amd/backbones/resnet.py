@@ -13,9 +13,17 @@ are explicit launch sequences on NHWC fp32 activations:
   convolution (``ops.subsample2`` + the existing 1x1 GEMM);
 * global average pool (``ops.global_avgpool``); the output is ``[B, 2048, 1, 1]`` as the reference returns it.
 
-Convolutions run in ``ops.conv_precision()`` arithmetic, weight gradients on the ``_WgradStream`` side stream.  Eval mode
-uses the running statistics through ``ops.bn_eval_coeffs`` and the same kernels.  The pre-split (P16) data flow and fused
-eval epilogues of the CLIP encoder are not built for this one.
+Convolutions run in ``ops.conv_precision()`` arithmetic, weight gradients on the ``_WgradStream`` side stream.
+
+Eval mode without gradients (``engine.inference``, ``Model.encode_images``) runs the pre-split (P16) data flow of the CLIP
+encoder's eval pass (``ResNet._run_forward_eval_p16``): a cached parameter-only plan, every convolution ONE
+launch whose epilogue applies the running-statistics BatchNorm, adds the residual, clamps and writes the next P16 operand scaled
+by an analytic bound - stem (``ops.stem7_eval_p16``), max pool on the P16 tensor (``ops.maxpool3s2_p16``), stride-2 3x3
+convolutions (``ops.conv3x3_s2_eval_p16``), ``ops.subsample2_p16`` in front of the stride-2 downsample convolutions, everything
+else ``ops.conv_eval_p16``, and ``ops.global_avgpool_p16``.  ``TRID_EVAL_P16=0``, the other arithmetic modes and shapes
+``eval_p16_ok`` declines run the training data flow on running-statistics coefficients (``ops.bn_eval_coeffs``, one ``bn_apply``
+pass per convolution).  The training pass itself keeps fp32 activations: the P16 TRAINING flow of the CLIP encoder is not built
+for this one.
 """
 
 import logging
@@ -26,7 +34,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .m_resnet import ConvArith, _bn_coeffs, _g3x3, _w3x3, _WgradStream, weight_amax
+from .m_resnet import ConvArith, _bn_coeffs, _g3x3, _w3x3, _WgradStream, p16_eligible, p16_weights, weight_amax
 
 
 class Bottleneck(nn.Module):
@@ -141,6 +149,30 @@ def block_backward(blk, rec, g, ar, ws, G):
     return dx
 
 
+P16_LIMIT_BYTES = 1 << 31  # the P16 kernels address their operands with 31-bit byte offsets
+
+
+def eval_p16_shape_ok(B, Hi, Wi):
+    """Do the eval-mode P16 kernels take a [B, 3, Hi, Wi] batch?  True while the image batch and the two largest activations of
+    the pass - the stem's output [B, Ho, Wo, 64] and layer1's block outputs [B, Hp, Wp, 256], 4 bytes per element, with
+    Ho = (Hi - 1) // 2 + 1 and Hp = (Ho - 1) // 2 + 1 (likewise Wo, Wp) - each stay below P16_LIMIT_BYTES (2 GB: B <= 682 at
+    384 x 128); every map size, odd ones included, is covered.  Larger batches are declined (the unfused path takes them)."""
+    if B < 1 or Hi < 1 or Wi < 1:
+        return False
+    Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+    Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
+    return max(B * 3 * Hi * Wi, B * Ho * Wo * 64, B * Hp * Wp * 256) * 4 < P16_LIMIT_BYTES
+
+
+def eval_p16_ok(mod, images):
+    """The eligibility predicate of ResNet._run_forward_eval_p16: a contiguous fp32 [B, 3, Hi, Wi] batch of a size
+    eval_p16_shape_ok accepts, on a module whose block channel counts are multiples of the 32-wide K group (every Bottleneck
+    architecture) behind the 3 -> 64 channel 7x7 stem."""
+    return (images.dim() == 4 and images.shape[1] == 3 and images.dtype == torch.float32 and images.is_contiguous()
+            and tuple(mod.conv1.weight.shape) == (64, 3, 7, 7) and mod.conv1.weight.is_contiguous() and p16_eligible(mod, 32)
+            and eval_p16_shape_ok(images.shape[0], images.shape[2], images.shape[3]))
+
+
 class _EncoderFn(torch.autograd.Function):
     """forward(images, module, save, *params) -> [B, 2048, 1, 1]; grads for every parameter (m_resnet._EncoderFn's contract)."""
 
@@ -240,9 +272,59 @@ class ResNet(nn.Module):
         save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         return _EncoderFn.apply(x, self, save, *params)
 
+    def _eval_plan(self, device):
+        """Everything of the eval-mode pass that depends on the parameters only, kept until a parameter or BatchNorm buffer is
+        replaced or written (m_resnet.ModifiedResNet._eval_plan's key: ops.parameter_generation(), data pointers, versions): the
+        P16 filters (one pack launch), the running-statistics BatchNorm coefficients of the 53 / 104 layers and the output-bound
+        coefficients of every convolution (one launch)."""
+        key = (device, ops.parameter_generation()) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        plan = getattr(self, "_eval_plan_cache", None)
+        if plan is not None and plan[0] == key:
+            return plan[1]
+        WA = weight_amax(self)
+        WP = p16_weights(self, WA, False, 1)
+        pairs = [(self.conv1, self.bn1)]
+        for blk in self.blocks():
+            pairs += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
+            if blk.downsample is not None:
+                pairs.append((blk.downsample[0], blk.downsample[1]))
+        sts = {id(bn): _bn_coeffs(bn, None, 0, False) for _, bn in pairs}
+        coef = ops.eval_bound_coefs([(conv.weight.detach(), sts[id(bn)].scale, sts[id(bn)].shift) for conv, bn in pairs], device)
+        # (the stem multiplies its fp32 filter as stored: no P16 copy)
+        E = {id(conv.weight): (WP.get(id(conv.weight)), sts[id(bn)], coef[i]) for i, (conv, bn) in enumerate(pairs)}
+        self._eval_plan_cache = (key, E, WA, coef)  # (WA / coef own the scalars the P16 filters and rows refer to)
+        return E
+
+    def _run_forward_eval_p16(self, images):
+        """Eval mode (test_net.py / inference.py:14-26) on pre-split (P16) activations from the stem to the pool, the data flow of
+        m_resnet.ModifiedResNet._run_forward_eval_p16: every convolution is ONE launch whose epilogue applies the running-statistics
+        BatchNorm, adds the P16 identity / downsample branch, clamps and writes the next operand as a P16 tensor scaled by the
+        analytic bound of csrc/gemm_common.h EvalBound; each epilogue folds the TRUE maximum of what it wrote into a device scalar
+        for the next bound.  No fp32 activation, no amax pass, no BatchNorm pass between the first and the last kernel; the only
+        passes that are not convolutions are the max pool, the three even-pixel subsamples and the global average pool."""
+        E = self._eval_plan(images.device)
+        _, st1, c1 = E[id(self.conv1.weight)]
+        a1 = ops.stem7_eval_p16(images, self.conv1.weight.detach(), st1, c1, ops.amax(images))
+        x = ops.maxpool3s2_p16(a1)
+        for blk in self.blocks():
+            aa = ops.conv_eval_p16(x, *E[id(blk.conv1.weight)], relu=True)
+            if blk.stride > 1:
+                ab = ops.conv3x3_s2_eval_p16(aa, *E[id(blk.conv2.weight)], relu=True)
+            else:
+                ab = ops.conv_eval_p16(aa, *E[id(blk.conv2.weight)], relu=True, conv3=True)
+            ident = x
+            if blk.downsample is not None:
+                xd = ops.subsample2_p16(x) if blk.stride > 1 else x  # the pixels a stride-2 1x1 convolution reads
+                ident = ops.conv_eval_p16(xd, *E[id(blk.downsample[0].weight)], relu=False)
+            x = ops.conv_eval_p16(ab, *E[id(blk.conv3.weight)], relu=True, res=ident)
+        feat = ops.global_avgpool_p16(x)
+        return feat.view(feat.shape[0], feat.shape[1], 1, 1)
+
     def _run_forward(self, images, save):
         training = self.training
         cp = ops.conv_precision()
+        if not training and not save and ops.USE_EVAL_P16 and ops.USE_P16 and cp == 16 and eval_p16_ok(self, images):
+            return self._run_forward_eval_p16(images), None
         ar = ConvArith(images.device, weight_amax(self) if cp in (16, 1) else {}, 1 if cp == 1 else None)
         nbt = []  # num_batches_tracked buffers, incremented together at the end of the pass
         # ---- stem (resnet.py:156-159)

@@ -29,6 +29,7 @@
 namespace trid {
 
 constexpr int P16_BK = 32;
+constexpr int A_CONV_S2 = 3;  // AMODE of gemm_p16_kernel only (not a trid_gemm_desc loader mode)
 
 // LDS of a gemm_p16_kernel workgroup: the operand stages - and, for the 12-wave tile that has a CU to itself anyway, room for the
 // whole fp32 tile of the staged (whole-row) epilogue
@@ -66,6 +67,8 @@ __device__ __forceinline__ void dma16_asm(const v4i_t& rs, unsigned lds_byte_add
 }
 
 // AMODE: A_KC (rows = GEMM rows) or A_CONV (rows = pixels of an NHWC image, K = 9 taps x Cin, 3x3 / stride 1 / pad 1)
+// or A_CONV_S2 (the same gather at stride 2: rows = OUTPUT pixels, the forward map of gemm.hip's CS = 1 loader; its own
+// instantiations - the others are the kernels they were)
 // PL = 2: P16 operands (two fp16 planes, 32 k per 128-byte row chunk, 3 MFMA products per multiply-add: fp32-class);
 // PL = 1: plain bf16 operands (64 k per 128-byte chunk, one bf16 MFMA per product): configs[3]'s bf16 arithmetic on
 // tensors their producers already wrote in bf16 - half the operand bytes, a third of the matrix work.
@@ -75,6 +78,7 @@ __device__ __forceinline__ void dma16_asm(const v4i_t& rs, unsigned lds_byte_add
 template <int AMODE, int BM, int BN, int WM, int WN, int STAGES, int PL, bool PP = false, int SP = 0>
 __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (WM * WN == 8 && (BM + BN) * 128 * STAGES <= 80 * 1024 ? 4 : ((WM * WN == 6 || WM * WN == 12) ? 3 : 2))) void gemm_p16_kernel(GemmParams p) {
     constexpr int NW = WM * WN;
+    constexpr bool CONV = AMODE == A_CONV || AMODE == A_CONV_S2, S2 = AMODE == A_CONV_S2;
     constexpr int BKE = PL == 2 ? 32 : 64;  // K elements per 128-byte row chunk = per K tile
     constexpr int EB = PL == 2 ? 4 : 2;     // bytes per element of a row
     constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
@@ -119,9 +123,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
 
     // ---- loader lanes: chunk c covers tile rows 8c .. 8c+7; lane -> (row 8c + lane/8, stored slot lane%8)
     constexpr unsigned OOB = 0x80000000u;
-    const long long a_ld_bytes = (AMODE == A_CONV ? (long long)p.Cin : p.lda) * EB;
-    const long long a_rows = (AMODE == A_CONV) ? (long long)p.M + 2 * p.W + 2 : p.M;
-    const char* a_base = (AMODE == A_CONV) ? A - (long long)(p.W + 1) * a_ld_bytes : A;  // tap offsets stay >= 0
+    const long long a_ld_bytes = (CONV ? (long long)p.Cin : p.lda) * EB;
+    // (A_CONV_S2: M counts OUTPUT pixels of the [RH][RW] map, the gathered tensor is the [H][W] source map)
+    const long long a_rows = CONV ? (S2 ? (long long)(p.M / (p.RH * p.RW)) * p.H * p.W : (long long)p.M) + 2 * p.W + 2 : p.M;
+    const char* a_base = (CONV) ? A - (long long)(p.W + 1) * a_ld_bytes : A;  // tap offsets stay >= 0
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, (unsigned)(a_rows * a_ld_bytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, 0, (unsigned)((long long)p.N * p.ldb * EB), 0x00020000);
 
@@ -134,7 +139,24 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
         const int m = m0 + r;
         voA[j] = (c < A_CH && m < p.M) ? (unsigned)((long long)m * a_ld_bytes + 16 * s) : OOB;
         amask[j] = 0x1ffu;
-        if (AMODE == A_CONV) {
+        if constexpr (S2) {
+            // stride 2: row m = output pixel (b, y, x) of the [RH][RW] map (fdW / fdH divide by RW / RH); its base is source pixel
+            // (2y, 2x) - with a_base one source row and one pixel back, tap (ky,kx) lands on (2y-1+ky, 2x-1+kx) at the stride-1 offsets
+            const uint32_t mm = m < p.M ? (uint32_t)m : 0u;
+            const uint32_t q = fdiv(mm, p.fdW);
+            const int x = (int)mm - (int)q * p.RW;
+            const uint32_t b = fdiv(q, p.fdH);
+            const int y = (int)q - (int)b * p.RH;
+            const long long src = ((long long)b * p.H + 2 * y) * p.W + 2 * x;
+            voA[j] = (c < A_CH && m < p.M) ? (unsigned)(src * a_ld_bytes + 16 * s) : OOB;
+            unsigned mk = 0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = 2 * y + t / 3 - 1, xx = 2 * x + t % 3 - 1;
+                if (yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) mk |= 1u << t;
+            }
+            amask[j] = mk;
+        } else if (CONV) {
             const uint32_t q = fdiv((uint32_t)m, p.fdW);
             const int x = m - (int)q * p.W;
             const uint32_t b = fdiv(q, p.fdH);
@@ -156,7 +178,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
         const int n = n0 + r;
         voB[j] = (c < B_CH && n < p.N) ? (unsigned)((long long)n * p.ldb * EB + 16 * s) : OOB;
     }
-    const int cgroups = (AMODE == A_CONV) ? p.Cin / BKE : 1;
+    const int cgroups = (CONV) ? p.Cin / BKE : 1;
 
     const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;  // LDS byte address of the stages
     auto issue = [&](int kt, int stage) {
@@ -164,7 +186,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
         uint4* sB = sA + BM * 8;
         unsigned soA, soB;
         int tap = 0;
-        if (AMODE == A_CONV) {
+        if (CONV) {
             // channel-group-major K order: all 9 taps of one 32-channel slab back to back (the nine shifted re-reads
             // of an activation slab are adjacent in time: L1/L2 hits); the weights' K index is (tap, channel)
             tap = kt % 9;
@@ -179,7 +201,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
             const int c = j * NW + wave;
             if (A_CH % NW != 0 && c >= A_CH) break;
             unsigned vo = voA[j];
-            if (AMODE == A_CONV) vo = ((amask[j] >> tap) & 1u) ? vo : OOB;
+            if (CONV) vo = ((amask[j] >> tap) & 1u) ? vo : OOB;
             dma16(rsA, sA + c * 64, vo, soA);
         }
 #pragma unroll
@@ -378,7 +400,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
         const unsigned cin_b = (unsigned)p.Cin * EB, roww_b = (unsigned)p.W * cin_b;
         {
             const int kt = kt_begin;
-            if (AMODE == A_CONV) {
+            if (CONV) {
                 n_tap = kt % 9;
                 const int cg = kt / 9;
                 n_dx = n_tap % 3;
@@ -396,7 +418,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
             c_soA = n_soA; c_soB = n_soB; c_tap = n_tap;
         };
         auto advance = [&]() {
-            if (AMODE == A_CONV) {
+            if (CONV) {
                 // (tap, channel group) -> next: taps innermost (gemm order: all 9 taps of a 32-channel slab back to back)
                 ++n_tap; ++n_dx;
                 n_soB += (unsigned)cgroups * 128u;
@@ -412,7 +434,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
                 const int c = q * NW + wave;
                 if (A_CH % NW != 0 && c >= A_CH) return;
                 unsigned vo = voA[q];
-                if (AMODE == A_CONV) vo = ((amask[q] >> c_tap) & 1u) ? vo : OOB;
+                if (CONV) vo = ((amask[q] >> c_tap) & 1u) ? vo : OOB;
                 dma16_asm(rsA_s, smem_base + (unsigned)(stage * STAGE_SLOTS + c * 64) * 16u, vo, c_soA);
             } else {
                 const int j = q - A_PW, c = j * NW + wave;
@@ -1607,4 +1629,48 @@ extern "C" int trid_gemm_p16(const trid_gemm_desc* d, int variant, void* stream_
     p.sSplit = d->strideSplit;
     if (d->a_mode == A_CONV) return pick_p16<A_CONV>(p, variant, planes, stream);
     return pick_p16<A_KC>(p, variant, planes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- stride-2 3x3, eval epilogue
+// layer{2,3,4}.0.conv2 of the ImageNet ResNet under model.eval() (reference resnet.py:62-70, 85-87): the A_CONV_S2 loader in front
+// of the 128 x 128 software-pipelined tile and its eval epilogue (c_fmt 1) - one launch, P16 in, P16 out.
+static bool conv3x3_s2_eval_ok(int B, int H, int W, int Cin, int Cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 != 0 || Cout % 32 != 0) return false;
+    const long long Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    return ((long long)B * H * W + 2 * W + 2) * Cin * 4 < (1ll << 31) && (long long)B * Ho * Wo * Cout * 4 < (1ll << 31) &&
+           (long long)Cout * 9 * Cin * 4 < (1ll << 31);
+}
+
+extern "C" int trid_conv3x3_s2_eval_p16_ok(int B, int H, int W, int Cin, int Cout) { return conv3x3_s2_eval_ok(B, H, W, Cin, Cout) ? 1 : 0; }
+
+extern "C" int trid_conv3x3_s2_eval_p16(const void* x, const float* x_amax, const void* w, const float* w_amax, const float* bn_scale,
+                                        const float* bn_shift, void* out, const float* eval_coef, const float* eval_tin, float* out_bound,
+                                        float* out_tmax, int B, int H, int W, int Cin, int Cout, int relu, void* stream) {
+    TRID_REQUIRE(x && x_amax && w && w_amax && bn_scale && bn_shift && out && eval_coef && eval_tin, "trid_conv3x3_s2_eval_p16: null pointer");
+    TRID_REQUIRE(aligned16(x) && aligned16(w) && aligned16(out) && aligned16(bn_scale) && aligned16(bn_shift),
+                 "trid_conv3x3_s2_eval_p16: operands must be 16-byte aligned");
+    TRID_REQUIRE(conv3x3_s2_eval_ok(B, H, W, Cin, Cout),
+                 "trid_conv3x3_s2_eval_p16: needs Cin %% 32 == 0, Cout %% 32 == 0 and tensors below 2 GB (B=%d H=%d W=%d Cin=%d Cout=%d)", B, H, W, Cin, Cout);
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.RH = (H - 1) / 2 + 1;
+    p.RW = (W - 1) / 2 + 1;
+    p.SH = H; p.SW = W;
+    p.A = reinterpret_cast<const float*>(x); p.B = reinterpret_cast<const float*>(w); p.C = reinterpret_cast<float*>(out);
+    p.M = B * p.RH * p.RW; p.N = Cout; p.K = 9 * Cin;
+    p.lda = Cin; p.ldb = p.K; p.ldc = Cout;
+    p.batch = 1; p.splits = 1;
+    p.k_chunk = p.K;
+    p.alpha = 1.f;
+    p.relu = relu;
+    p.H = H; p.W = W; p.Cin = Cin;          // the SOURCE map: tap offsets and the descriptor's range
+    p.fdW = make_fastdiv((uint32_t)p.RW);   // rows are pixels of the output map
+    p.fdH = make_fastdiv((uint32_t)p.RH);
+    p.a_amax = x_amax; p.b_amax = w_amax;
+    p.stats_w = 2;
+    p.c_fmt = 1;
+    p.wide_epilogue = 1;
+    p.colscale = bn_scale; p.bias = bn_shift;
+    p.ev.coef = eval_coef; p.ev.tin = eval_tin; p.ev.out_bound = out_bound; p.ev.out_tmax = out_tmax;
+    return launch_p16<A_CONV_S2, 128, 128, 2, 4, 2, 2, false, 2>(p, (hipStream_t)stream);
 }

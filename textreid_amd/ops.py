@@ -553,7 +553,7 @@ def bn_apply_p16(y, st, bound, relu=True, res=None, res_st=None, bound_res=None,
 
 
 # --------------------------------------------------------------------------- eval mode: fused epilogues writing P16
-USE_EVAL_P16 = os.environ.get("TRID_EVAL_P16", "1") != "0"  # eval-mode image encoder on the P16 kernels (0: the folded on-the-fly-split path, A/B runs)
+USE_EVAL_P16 = os.environ.get("TRID_EVAL_P16", "1") != "0"  # eval-mode image encoders on the P16 kernels (0: the folded on-the-fly-split path / the ImageNet ResNet's unfused pass, A/B runs)
 
 
 def eval_bound_coefs(entries, device):
@@ -1082,6 +1082,74 @@ def global_avgpool_bwd(g, H, W):
     dx = empty((Bi, H, W, C), g)
     call("trid_global_avgpool_bwd_f32", _p(g.contiguous()), _p(dx), Bi, H * W, C, stream())
     return dx
+
+
+# ... under model.eval() on P16 activations (csrc/resnet_eval.hip, the A_CONV_S2 loader of csrc/gemm_p16.hip): fused epilogues
+# with the scale / maximum scalars of conv_eval_p16
+def stem7_eval_p16(images, w, st, coef, img_amax, relu=True):
+    """Eval-mode stem convolution (3 -> 64, 7x7, stride 2, pad 3) + BatchNorm + ReLU straight from the NCHW batch -> P16
+    [B,Ho,Wo,64]; img_amax: device scalar >= max|images| (ops.amax); coef: this convolution's row of eval_bound_coefs."""
+    Bi, Cin, Hi, Wi = images.shape
+    if Cin != 3 or tuple(w.shape) != (64, 3, 7, 7) or not w.is_contiguous() or not images.is_contiguous():
+        raise RuntimeError("stem7_eval_p16: a contiguous [B,3,H,W] image batch and contiguous [64,3,7,7] filters are needed")
+    out = p16_empty((Bi, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1, 64), images, 1)
+    bound, tmax = amax_slot(images.device), amax_slot(images.device)
+    call("trid_stem7_eval_p16", _p(images), _p(w), _p(st.scale), _p(st.shift), _p(out), _p(coef), _p(img_amax), _p(bound), _p(tmax),
+         Bi, Hi, Wi, 1 if relu else 0, stream())
+    return P16(out, bound, 1, tmax)
+
+
+def maxpool3s2_p16(x):
+    """maxpool(3, stride 2, pad 1) of a P16 tensor x [B,H,W,C] -> P16 [B,(H-1)//2+1,(W-1)//2+1,C] at x's scale (the winner's
+    two fp16 parts are copied: unpack(out) == max_pool2d(unpack(x)) exactly); `.tmax` is the true maximum of the output."""
+    Bi, H, W, C = x.shape
+    if x.fmt != 1:
+        raise RuntimeError("maxpool3s2_p16: a P16 (fmt 1) tensor is needed")
+    out = p16_empty((Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), x.data, 1)
+    tmax = amax_slot(x.data.device)
+    call("trid_maxpool3s2_p16", _p(x.data), _p(x.amax), _p(out), _p(tmax), Bi, H, W, C, stream())
+    return P16(out, x.amax, 1, tmax)
+
+
+def conv3x3_s2_eval_ok(Bi, H, W, Cin, Cout):
+    """Does conv3x3_s2_eval_p16 take this geometry?  (channel counts in multiples of 32, every tensor below 2 GB)"""
+    return bool(_query("trid_conv3x3_s2_eval_p16_ok", int(Bi), int(H), int(W), int(Cin), int(Cout)))
+
+
+def conv3x3_s2_eval_p16(x, w, st, coef, relu=True):
+    """Eval-mode 3x3 / stride 2 / pad 1 convolution + BatchNorm(running statistics) (+ ReLU) in ONE kernel, P16 in -> P16 out:
+    x P16 [B,H,W,Cin] with its true maximum `x.tmax`, w P16 [Cout, 9*Cin] -> P16 [B,(H-1)//2+1,(W-1)//2+1,Cout]; scalars as in
+    conv_eval_p16."""
+    Bi, H, W, C = x.shape
+    N = w.shape[0]
+    if x.fmt != 1 or w.fmt != 1 or w.shape[1] != 9 * C or not conv3x3_s2_eval_ok(Bi, H, W, C, N):
+        raise RuntimeError("conv3x3_s2_eval_p16: geometry B=%d H=%d W=%d Cin=%d Cout=%d (or a non-P16 operand) is not covered" % (Bi, H, W, C, N))
+    out = p16_empty((Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, N), x.data, 1)
+    bound, tmax = amax_slot(x.data.device), amax_slot(x.data.device)
+    call("trid_conv3x3_s2_eval_p16", _p(x.data), _p(x.amax), _p(w.data), _p(w.amax), _p(st.scale), _p(st.shift), _p(out), _p(coef), _p(x.tmax),
+         _p(bound), _p(tmax), Bi, H, W, C, N, 1 if relu else 0, stream())
+    return P16(out, bound, 1, tmax)
+
+
+def subsample2_p16(x):
+    """P16 x [B,H,W,C] -> its even rows and columns as a P16 tensor with the same scale scalar (whole rows copied); x's true
+    maximum still bounds the output."""
+    Bi, H, W, C = x.shape
+    if x.fmt != 1:
+        raise RuntimeError("subsample2_p16: a P16 (fmt 1) tensor is needed")
+    out = p16_empty((Bi, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), x.data, 1)
+    call("trid_subsample2_p16", _p(x.data), _p(out), Bi, H, W, C, stream())
+    return P16(out, x.amax, 1, x.tmax)
+
+
+def global_avgpool_p16(x):
+    """P16 x [B,H,W,C] -> fp32 [B,C], the mean over the pixels of the unpacked values (summed in pixel order, as global_avgpool)."""
+    Bi, H, W, C = x.shape
+    if x.fmt != 1:
+        raise RuntimeError("global_avgpool_p16: a P16 (fmt 1) tensor is needed")
+    out = empty((Bi, C), x.data)
+    call("trid_global_avgpool_p16", _p(x.data), _p(x.amax), _p(out), Bi, H * W, C, stream())
+    return out
 
 
 # --------------------------------------------------------------------------- BatchNorm
