@@ -761,6 +761,17 @@ int trid_sim_topk_f32(const float* q, const float* g, float* out_val, int64_t* o
 int trid_sim_topk_p16(const float* q, const float* g, const void* q16, const void* g16, float* out_val, int64_t* out_idx, int Q, int G,
                       int k, long long idx_offset, const float* q_amax, const float* g_amax, float* ws, int mode, void* stream);
 long long trid_topk_ws_flag_offset(int Q, int G);
+/* Small-batch search of a persistent gallery (textreid_amd/index.py GalleryIndex, csrc/gallery_index.hip): 1 <= Q <= 32 queries
+ * q16 = P16 [32][256] (rows >= Q zero) against g16 = P16 [G][256], BOTH packed with the one scalar unit_amax (unit rows: 1.0), in
+ * ONE pass over the gallery - no threshold panel, no segments, no host read.  Persistent workgroups own contiguous row ranges and
+ * keep the query panel in registers; each leaves a sorted list of k per query in ws, a second launch merges them.  Values are
+ * bit-identical to trid_gemm_p16 on the same operands; order: value descending, then row ascending, whatever the partition.
+ * out_val [Q,k] f32, out_idx [Q,k] i64 (+ idx_offset).  k <= 16, k <= G, G * 1024 < 2^31, operands 16-byte aligned.
+ * workgroups: 0 = the library's choice, > 0 forces that many workers (tests, tuning); ws bytes >= trid_index_search_ws_bytes
+ * with the same arguments (0 for arguments out of range). */
+long long trid_index_search_ws_bytes(int G, int Q, int k, int workgroups);
+int trid_index_search_p16(const void* q16, const void* g16, const float* unit_amax, int Q, int G, int k,
+                          long long idx_offset, float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream);
 
 /* per-row top-k of a given similarity matrix (rank(get_mAP=False), evaluation.py:17-19) */
 int trid_topk_rows_f32(const float* sim, int ld, int Q, int G, int k, float* out_val, int64_t* out_idx,

@@ -1,0 +1,1 @@
+from .index import GalleryIndex  # noqa: F401

@@ -1,0 +1,341 @@
+// GalleryIndex search (textreid_amd/index.py): the top-k of at most 32 queries against a persistent P16 gallery in ONE pass.
+//
+// The retrieval filter of gemm_stream.hip (FUSE 4) is built for Q = 1e4: 256 resident queries per workgroup on 8 column waves, a
+// threshold taken from a first panel, candidate lists in global memory and merges between growing segments.  For a handful of
+// queries seven of its eight column waves multiply zero padding.  Here
+//   * the whole query panel (32 queries x K = 256, 32 KB) is ONE set of MFMA B fragments, 128 VGPRs, resident in EVERY wave;
+//   * the waves of a workgroup split the gallery ROWS: a step tile is IX_NW x 32 rows, each wave brings its own 32 rows in by
+//     LDS-DMA into a private two-slot ring (16-byte units XOR-swizzled by the row, as gemm_stream.hip) - no barrier in the loop;
+//   * persistent workgroups own contiguous ranges of step tiles: every gallery row is read from HBM exactly once;
+//   * selection needs no earlier pass: a lane keeps a running threshold of its query (from -inf), appends the rare elements above
+//     it to a lane-private staging list in LDS and folds the list into a sorted list of 16 in registers when it fills;
+//   * a workgroup leaves one sorted list of k per query; a second launch merges the workgroups' lists.
+// Arithmetic and product order are those of gemm_p16_kernel<A_KC> (hi*lo + lo*hi + hi*hi per 16-deep k step, k ascending, gallery
+// = A, queries = B): the similarities are bit-identical to trid_gemm_p16 on the same operands.
+// ONE order everywhere: value descending, then gallery row ascending - the result does not depend on the partition.
+
+#include <algorithm>
+#include <mutex>
+
+#include "split_common.h"
+#include "topk_wave.h"
+
+namespace trid {
+
+namespace {
+
+constexpr int IX_NW = 2;                  // waves per workgroup (two private rings of 2 x 32 KB fill the LDS)
+constexpr int IX_RB = IX_NW * 32;         // gallery rows per step tile
+constexpr int IX_ROWB = 1024;             // bytes of one P16 row (K = 256)
+constexpr int IX_SLOT = 32 * IX_ROWB;     // one wave's tile
+constexpr int IX_SCAP = 24;               // staging entries per lane: a fold is due at IX_FOLD, one tile adds at most 16
+constexpr int IX_FOLD = 8;
+constexpr int IX_STG = IX_SCAP * 64 * 8;  // bytes of one wave's staging lists, [entry][lane] x (value, row)
+constexpr int IX_LDS = IX_NW * 2 * IX_SLOT + IX_NW * IX_STG;
+constexpr int IX_MAX_WORKERS = 4096;
+constexpr int IX_CUS = 256;
+static_assert(IX_SCAP >= IX_FOLD - 1 + 16 && IX_SCAP >= TOPK_MAX, "staging list: one tile beyond the fold mark, and the final lists");
+static_assert(IX_LDS <= 160 * 1024, "LDS of one CU");
+
+struct IxParams {
+    const char* q16;    // P16 [32][256], rows >= Q zero
+    const char* g16;    // P16 [G][256]
+    const float* unit;  // the amax both were packed with
+    float* wval;        // [Q][W][k]
+    int* wrow;          // [Q][W][k]
+    int Q, G, k, W, tiles;
+};
+
+__device__ __forceinline__ void ix_dma16(const __amdgpu_buffer_rsrc_t& rs, void* lds_base, unsigned voffset) {
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_base, 16, voffset, 0, 0, 0);
+}
+// (inline asm: beside an LDS-DMA in flight hipcc orders a visible LDS access behind s_waitcnt vmcnt(0))
+__device__ __forceinline__ void ix_lds_store(unsigned addr, unsigned v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
+__device__ __forceinline__ unsigned ix_lds_load(unsigned addr) {
+    unsigned r;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(addr) : "memory");
+    return r;
+}
+
+// "a comes before b": value descending, then row ascending (empty slots are -inf / -1: behind every real pair)
+__device__ __forceinline__ bool ix_before(float av, int ar, float bv, int br) { return av > bv || (av == bv && (unsigned)ar < (unsigned)br); }
+
+}  // namespace
+
+__global__ __launch_bounds__(IX_NW * 64) void index_search_kernel(IxParams p) {
+    constexpr int KG = 8;
+    extern __shared__ __attribute__((aligned(16))) uint4 ix_smem[];
+    char* const lds = reinterpret_cast<char*>(ix_smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int khalf = lane >> 5;
+    char* const ring = lds + wave * (2 * IX_SLOT);
+    char* const stg_all = lds + IX_NW * 2 * IX_SLOT;
+    // this lane's staging entry 0; entries are 512 bytes apart (one VGPR: see gemm_stream.hip f_wbuf)
+    unsigned stg = (unsigned)(uintptr_t)(stg_all + wave * IX_STG) + (unsigned)lane * 8u;
+    asm volatile("" : "+v"(stg));
+
+    // this worker's contiguous range of step tiles
+    const int w = blockIdx.x;
+    const int t0 = (int)((long long)w * p.tiles / p.W), t1 = (int)((long long)(w + 1) * p.tiles / p.W);
+
+    const float s = f16_scale_of(*p.unit);
+    const float unscale = 1.f / (s * s);
+
+    // the query panel: [k group][k step][plane] fragments, 128 VGPRs
+    f16x8 bf[KG][2][2];
+    {
+        const char* br = p.q16 + (size_t)(lane & 31) * IX_ROWB;
+#pragma unroll
+        for (int g = 0; g < KG; ++g)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl)
+                    bf[g][ks][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(br + g * 128 + (4 * pl + 2 * ks + khalf) * 16));
+    }
+    const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc((void*)p.g16, 0, (unsigned)((size_t)p.G * IX_ROWB), 0x00020000);
+    constexpr unsigned OOB = 0x80000000u;
+
+    // running threshold of this lane's query: -inf admits everything; the zero padding columns of the panel admit nothing
+    const bool q_live = (lane & 31) < p.Q;
+    float f_thr = q_live ? -INFINITY : INFINITY;
+    // this lane's sorted list: the best 16 pairs among the rows IT saw (its query, the rows of its k half); the first k count
+    float lv[TOPK_MAX];
+    int lr[TOPK_MAX];
+#pragma unroll
+    for (int i = 0; i < TOPK_MAX; ++i) {
+        lv[i] = -INFINITY;
+        lr[i] = -1;
+    }
+    int cnt = 0;  // staged entries of this lane
+
+    // one DMA instruction = one gallery row (64 units of 16 bytes); lane = stored unit, source unit = lane ^ (row & 15).  Rows
+    // beyond G lie beyond the descriptor's range: the slot reads zeros there
+    auto issue = [&](int tile, int slot, int zero) {
+        const int ln = lane + zero;
+        const int row0 = tile * IX_RB + wave * 32;
+        char* dst = ring + slot * IX_SLOT;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) {
+            const int row = row0 + d;
+            ix_dma16(rsG, dst + d * IX_ROWB, row < p.G ? (unsigned)row * (unsigned)IX_ROWB + (unsigned)((ln ^ (d & 15)) << 4) : OOB);
+        }
+    };
+
+    // staged pairs -> the sorted list (one pair per lane and round, every lane its own), then the tightened threshold
+    auto fold = [&]() {
+        const int nmax = __builtin_amdgcn_readfirstlane((int)wave_max((float)cnt));
+        for (int e = 0; e < nmax; ++e) {
+            const bool has = e < cnt;
+            float cv = -INFINITY;
+            int cr = -1;
+            if (has) {
+                cv = __uint_as_float(ix_lds_load(stg + 512u * (unsigned)e));
+                cr = (int)ix_lds_load(stg + 512u * (unsigned)e + 4u);
+            }
+#pragma unroll
+            for (int i = 0; i < TOPK_MAX; ++i) {
+                const bool b = ix_before(cv, cr, lv[i], lr[i]);
+                const float tv = lv[i];
+                const int tr = lr[i];
+                lv[i] = b ? cv : tv;
+                lr[i] = b ? cr : tr;
+                cv = b ? tv : cv;
+                cr = b ? tr : cr;
+            }
+        }
+        cnt = 0;
+        float kth = lv[0];
+#pragma unroll
+        for (int i = 1; i < TOPK_MAX; ++i) kth = (i == p.k - 1) ? lv[i] : kth;
+        // the k-th best of EITHER half of the query's rows bounds the k-th best of all of them from below
+        kth = fmaxf(kth, __shfl_xor(kth, 32, 64));
+        if (q_live) f_thr = kth;
+    };
+
+    const int a_off = (lane & 31) * IX_ROWB;
+    const int rsw = lane & 15;
+
+    // the panel's loads are waited for HERE, by an instruction the compiler accounts for (gemm_stream.hip, same place)
+#pragma unroll
+    for (int g = 0; g < KG; ++g)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) asm volatile("" : "+v"(bf[g][ks][pl]));
+    asm volatile("" : "+v"(f_thr));
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+
+    if (t0 < t1) issue(t0, 0, 0);
+    int slot = 0;
+    for (int t = t0; t < t1; ++t, slot ^= 1) {
+        // this wave's own DMA of tile t: its covering vmcnt orders it for this wave's reads
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        // the other slot was last read by the MFMAs of tile t - 1, all issued: free
+        if (t + 1 < t1) issue(t + 1, slot ^ 1, zero);
+
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        const char* sA = ring + slot * IX_SLOT;
+        f16x8 af[2][2];
+        auto fetch = [&](int q, f16x8(&dst)[2]) {  // q = k group * 2 + k step
+            const int g = q >> 1, ks = q & 1;
+            const int u0 = g * 8 + 2 * ks + khalf;
+            dst[0] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sA + a_off + ((u0 ^ rsw) << 4)));
+            dst[1] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sA + a_off + (((u0 + 4) ^ rsw) << 4)));
+        };
+        fetch(0, af[0]);
+#pragma unroll
+        for (int q = 0; q < 2 * KG; ++q) {
+            if (q + 1 < 2 * KG) fetch(q + 1, af[(q + 1) & 1]);
+            const int g = q >> 1, ks = q & 1;
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q & 1][0], bf[g][ks][1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q & 1][1], bf[g][ks][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q & 1][0], bf[g][ks][0], acc, 0, 0, 0);
+        }
+
+        // ---- selection: element r of the accumulator = (gallery row rb + (r & 3) + 8 (r >> 2), query lane & 31)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] *= unscale;
+        const int rb = t * IX_RB + wave * 32 + 4 * khalf;
+        if ((t + 1) * IX_RB > p.G) {  // (a ragged last tile read zeros: never candidates)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (rb + (r & 3) + 8 * (r >> 2) >= p.G) acc[r] = -INFINITY;
+        }
+        float mx = acc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[r]);
+        // rows ascend with time: a later element that only EQUALS the k-th best loses the tie - strictly above the threshold
+        if (__ballot(mx > f_thr) != 0ull) {
+            if (mx > f_thr) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if (acc[r] > f_thr) {
+                        const unsigned a = stg + 512u * (unsigned)cnt;
+                        ix_lds_store(a, __float_as_uint(acc[r]));
+                        ix_lds_store(a + 4u, (unsigned)(rb + (r & 3) + 8 * (r >> 2)));
+                        ++cnt;
+                    }
+                }
+            }
+            if (__ballot(cnt >= IX_FOLD) != 0ull) fold();
+        }
+    }
+    fold();
+
+    // ---- the workgroup's list of k per query: the 2 x IX_NW sorted lane lists of the query, merged by lane `query` of wave 0
+#pragma unroll
+    for (int i = 0; i < TOPK_MAX; ++i) {
+        ix_lds_store(stg + 512u * (unsigned)i, __float_as_uint(lv[i]));
+        ix_lds_store(stg + 512u * (unsigned)i + 4u, (unsigned)lr[i]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (wave == 0 && lane < p.Q) {
+        constexpr int NL = 2 * IX_NW;
+        int head[NL];
+        const float2* src[NL];
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            head[l] = 0;
+            src[l] = reinterpret_cast<const float2*>(stg_all + (l >> 1) * IX_STG) + lane + 32 * (l & 1);  // entry e at src[l][64 e]
+        }
+        float* ov = p.wval + ((long long)lane * p.W + w) * p.k;
+        int* orow = p.wrow + ((long long)lane * p.W + w) * p.k;
+        for (int j = 0; j < p.k; ++j) {
+            float bv = -INFINITY;
+            int br = -1, bl = 0;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                if (head[l] < TOPK_MAX) {
+                    const float2 e = src[l][64 * head[l]];
+                    const int er = __float_as_int(e.y);
+                    if (ix_before(e.x, er, bv, br)) {
+                        bv = e.x;
+                        br = er;
+                        bl = l;
+                    }
+                }
+            }
+#pragma unroll
+            for (int l = 0; l < NL; ++l) head[l] += (l == bl && br >= 0) ? 1 : 0;
+            ov[j] = bv;
+            orow[j] = br;
+        }
+    }
+}
+
+// pass 2: one wave per query folds the W x k pairs the workers left (empty slots -inf / -1 are skipped) into the final list
+__global__ __launch_bounds__(256) void index_merge_kernel(const float* __restrict__ wval, const int* __restrict__ wrow, int Q, int n, int k,
+                                                          long long idx_offset, float* __restrict__ out_val, long long* __restrict__ out_idx) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) return;
+    WaveTopk<TOPK_MAX> L;
+    L.init(lane, nullptr, nullptr);
+    const float* v = wval + (long long)q * n;
+    const int* r = wrow + (long long)q * n;
+    for (int base = 0; base < n; base += 64) {
+        const bool in = base + lane < n;
+        const int row = in ? r[base + lane] : -1;
+        const float x = in ? v[base + lane] : -INFINITY;
+        L.offer_lanes(row >= 0, x, idx_offset + row);
+    }
+    if (lane < k) {
+        out_val[(long long)q * k + lane] = L.lv;
+        out_idx[(long long)q * k + lane] = L.li;
+    }
+}
+
+static int ix_workers(int G, int workgroups) {
+    if (workgroups > 0) return workgroups;
+    const int tiles = (G + IX_RB - 1) / IX_RB;
+    return std::max(1, std::min(IX_CUS, tiles));  // one persistent workgroup per CU (its rings fill the LDS), no more than tiles
+}
+
+}  // namespace trid
+
+using namespace trid;
+
+extern "C" long long trid_index_search_ws_bytes(int G, int Q, int k, int workgroups) {
+    if (G <= 0 || Q <= 0 || k <= 0 || workgroups < 0 || workgroups > IX_MAX_WORKERS) return 0;
+    return (long long)ix_workers(G, workgroups) * Q * k * 8;
+}
+
+extern "C" int trid_index_search_p16(const void* q16, const void* g16, const float* unit_amax, int Q, int G, int k, long long idx_offset,
+                                     float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream) {
+    TRID_REQUIRE(q16 && g16 && unit_amax && out_val && out_idx && ws, "trid_index_search_p16: null operand");
+    TRID_REQUIRE(Q >= 1 && Q <= 32, "trid_index_search_p16: 1 <= Q <= 32 (Q=%d): larger batches go through trid_sim_topk_p16", Q);
+    TRID_REQUIRE(G >= 1 && (long long)G * IX_ROWB < (1ll << 31), "trid_index_search_p16: 1 <= G and G * 1024 < 2^31 (G=%d)", G);
+    TRID_REQUIRE(k >= 1 && k <= TOPK_MAX && k <= G, "trid_index_search_p16: k must be in [1,%d] and <= G (k=%d G=%d)", TOPK_MAX, k, G);
+    TRID_REQUIRE(workgroups >= 0 && workgroups <= IX_MAX_WORKERS, "trid_index_search_p16: 0 <= workgroups <= %d (workgroups=%d)", IX_MAX_WORKERS, workgroups);
+    TRID_REQUIRE(aligned16(q16) && aligned16(g16) && aligned16(ws), "trid_index_search_p16: operands must be 16-byte aligned");
+    static std::once_flag once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(once, [] {
+        attr_err = hipFuncSetAttribute((const void*)index_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    if (attr_err != hipSuccess) {
+        set_error("trid_index_search_p16: cannot reserve LDS: %s", hipGetErrorString(attr_err));
+        return (int)attr_err;
+    }
+    IxParams p;
+    p.q16 = (const char*)q16; p.g16 = (const char*)g16; p.unit = unit_amax;
+    p.Q = Q; p.G = G; p.k = k;
+    p.W = ix_workers(G, workgroups);
+    p.tiles = (G + IX_RB - 1) / IX_RB;
+    p.wval = reinterpret_cast<float*>(ws);
+    p.wrow = reinterpret_cast<int*>(p.wval + (long long)p.W * Q * k);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(index_search_kernel, dim3(p.W), dim3(IX_NW * 64), IX_LDS, s, p);
+    int rc = check_launch("trid_index_search_p16");
+    if (rc != TRID_OK) return rc;
+    hipLaunchKernelGGL(index_merge_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, p.wval, p.wrow, Q, p.W * k, k, idx_offset, out_val, reinterpret_cast<long long*>(out_idx));
+    return check_launch("trid_index_search_p16 (merge)");
+}

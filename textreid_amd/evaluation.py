@@ -73,31 +73,35 @@ def _metrics(indices, q_pids, g_pids, topk_t, get_mAP):
     return cmc, mAP[0], indices
 
 
-def _sim_precision(q, g):
+def _sim_precision(q, g, ga=None):
     """Arithmetic of the similarity GEMM: the fp16 two-plane split (half the MFMA work of the bf16 one, same fp32-class
     accuracy) while the library-wide mode is the fp32-class default; it needs the operands' largest magnitudes as
-    device scalars (one streaming pass each - the gallery pass is ~1 % of the scoring time)."""
+    device scalars (one streaming pass each - the gallery pass is ~1 % of the scoring time; ga: the gallery's scalar, already known)."""
     if ops.GEMM_PRECISION != 6 or ops.CONV_PRECISION != 16:
         return ops.GEMM_PRECISION, None, None
-    return 16, ops.amax(q), ops.amax(g)
+    return 16, ops.amax(q), (ops.amax(g) if ga is None else ga)
 
 
 USE_SIM_P16 = os.environ.get("TRID_SIM_P16", "1") != "0"  # retrieval match on pre-split operands (0: the on-the-fly split GEMM, A/B runs)
 DEVICE_GATED_FALLBACK = False  # True: the capture-safe form (fall-back passes gated on the device) outside a capture too (tests)
 
 
-def _sim_topk_call(q, g, vals, idx, k, offset, ws):
-    """The fused similarity + top-k launch sequence.  C == 256 embeddings in the fp32-class default arithmetic: the gallery (written
+def _sim_topk_call(q, g, vals, idx, k, offset, ws, g16=None, ga=None):
+    """The fused similarity + top-k launch sequence.  g16 / ga: the gallery already pre-split and the scalar it was packed with
+    (index.GalleryIndex holds both); by default the gallery is measured and packed here.  C == 256 embeddings in the fp32-class default arithmetic: the gallery (written
     once, scored against every query panel) and the queries are split into their fp16 planes ONCE (p16_pack) and the
     admission-filter pass runs on the streaming kernel with the queries resident in registers (trid_sim_topk_p16)."""
     Q, C = q.shape
     G = g.shape[0]
-    prec, qa, ga = _sim_precision(q, g)
+    if (g16 is None) != (ga is None):
+        raise ValueError("_sim_topk_call: g16 and ga go together")
+    prec, qa, ga = _sim_precision(q, g, ga)
     if USE_SIM_P16 and prec == 16 and C == 256 and G > 8192 and G * 1024 < (1 << 31):
         q16 = torch.zeros((Q + 31) // 32 * 32, C, dtype=torch.float32, device=q.device)
         call("trid_p16_pack_f32", _p(q), Q, C, C, _p(qa), _p(q16), 1, stream())
-        g16 = torch.empty_like(g)
-        call("trid_p16_pack_f32", _p(g), G, C, C, _p(ga), _p(g16), 1, stream())
+        if g16 is None:
+            g16 = torch.empty_like(g)
+            call("trid_p16_pack_f32", _p(g), G, C, C, _p(ga), _p(g16), 1, stream())
         if DEVICE_GATED_FALLBACK or torch.cuda.is_current_stream_capturing():  # (no host read inside a capture: the device-gated fall-back passes)
             call("trid_sim_topk_p16", _p(q), _p(g), _p(q16), _p(g16), _p(vals), _p(idx), Q, G, k, offset, _p(qa), _p(ga), _p(ws), 0, stream())
             return

@@ -1,0 +1,238 @@
+"""GalleryIndex: the deployed form of the retrieval match - a gallery held on the device that grows as images arrive, small
+query batches answered against it.
+
+``evaluation.similarity_topk`` normalises, measures and packs the whole gallery on every call and then runs a match built for
+Q = 1e4 queries.  The index pays those costs once per appended row: it keeps the L2-normalised fp32 rows and the same rows
+pre-split (P16, include/textreid_hip.h "P16").  Unit rows satisfy ``|x| <= 1``, so the P16 scale is the analytic one for
+``amax = 1.0`` - one constant device scalar that is never recomputed: appending never re-packs earlier rows.  ``search`` with
+at most 32 queries is ONE pass over the P16 gallery (csrc/gallery_index.hip, ``trid_index_search_p16``): no host read, no
+allocation but the outputs and a workspace cached on the index, so it can be recorded with ``torch.cuda.graph`` and replayed.
+Larger batches run the launch sequence of ``similarity_topk`` on the operands the index already holds.
+
+Order of the results: value descending, then row number ascending (row number = insertion order).
+
+An index is used from ONE stream: ``add`` and ``search`` run on torch's current stream and share the cached workspace.  A
+recorded search answers against the gallery as it stood at the capture (row count and storage are part of the recording):
+record again after an ``add``.
+
+Not built: row removal, gallery shards over ranks, widths other than 256, an image-encoder convenience wrapper (``add`` takes
+embeddings, e.g. the image half of ``inference`` output).
+"""
+
+import torch
+
+from . import ops
+from .ops import _p, call, stream
+
+DIM = 256
+MAX_ROWS = (1 << 21) - 1  # the 31-bit byte offsets of the P16 retrieval kernels: rows * 1024 < 2^31
+SMALL_Q = 32              # the panel width of trid_index_search_p16
+MAX_K = 16
+
+
+def _need_cuda(name, t):
+    if not t.is_cuda:
+        raise RuntimeError("textreid_amd.index.GalleryIndex.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
+
+
+class GalleryIndex:
+    """``idx = GalleryIndex(); idx.add(image_embed, pids); vals, rows = idx.search(text_embed, k=10)``.  See the module docstring
+    for the storage, the order rule, the one-stream rule and what is out of scope."""
+
+    def __init__(self, dim=DIM, capacity=0):
+        if dim != DIM:
+            raise ValueError("GalleryIndex: dim must be %d (every config has FEATURE_SIZE 256 and the P16 retrieval kernels are K = 256); got %d" % (DIM, dim))
+        if capacity < 0 or capacity > MAX_ROWS:
+            raise ValueError("GalleryIndex: capacity must be in [0, %d]; got %d" % (MAX_ROWS, capacity))
+        self.dim = dim
+        self._want = int(capacity)  # rows the first allocation holds at least
+        self._n = 0
+        self._rows = None   # fp32 [capacity, 256], L2-normalised
+        self._p16 = None    # the same rows, P16
+        self._pids = None   # int64 [capacity] once pids were given
+        self._has_pids = None
+        self._unit = None   # device scalar 1.0: the amax every row and every query is packed with
+        self._ws = {}       # the cached workspace of the small-batch search
+        self._panel_rows = 0  # rows of the cached query panel the last search wrote
+
+    # ------------------------------------------------------------------ storage
+    def __len__(self):
+        return self._n
+
+    @property
+    def capacity(self):
+        return 0 if self._rows is None else self._rows.shape[0]
+
+    @property
+    def device(self):
+        return None if self._rows is None else self._rows.device
+
+    @property
+    def rows(self):
+        """the normalised fp32 rows held, [len, 256] (a view of the storage)"""
+        return None if self._rows is None else self._rows[: self._n]
+
+    @property
+    def rows_p16(self):
+        """the same rows pre-split, [len, 256] (a view of the storage)"""
+        return None if self._p16 is None else self._p16[: self._n]
+
+    @property
+    def unit_amax(self):
+        return self._unit
+
+    @property
+    def pids(self):
+        return None if not self._has_pids or self._pids is None else self._pids[: self._n]
+
+    def _reserve(self, total, device):
+        if self._rows is not None and self._rows.device != device:
+            raise ValueError("GalleryIndex: the index lives on %s; got a tensor on %s" % (self._rows.device, device))
+        cap = self.capacity
+        if self._rows is not None and total <= cap:
+            return
+        new_cap = min(MAX_ROWS, max(total, self._want, 2 * cap, 64))
+        rows = torch.empty(new_cap, self.dim, dtype=torch.float32, device=device)
+        p16 = torch.empty(new_cap, self.dim, dtype=torch.float32, device=device)
+        pids = torch.empty(new_cap, dtype=torch.int64, device=device)
+        if self._n:
+            rows[: self._n].copy_(self._rows[: self._n])
+            p16[: self._n].copy_(self._p16[: self._n])
+            pids[: self._n].copy_(self._pids[: self._n])
+        self._rows, self._p16, self._pids = rows, p16, pids
+        if self._unit is None:
+            self._unit = torch.ones(1, dtype=torch.float32, device=device)
+
+    def _check_rows(self, name, x):
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError("GalleryIndex.%s: expected a [n, %d] tensor; got %s" % (name, self.dim, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        _need_cuda(name, x)
+        return x.contiguous().float()
+
+    def _pack_into(self, first, n):
+        dst = self._p16[first : first + n]
+        call("trid_p16_pack_f32", _p(self._rows[first:]), n, self.dim, self.dim, _p(self._unit), _p(dst), 1, stream())
+
+    def add(self, embeddings, pids=None, normalize=True):
+        """Append rows; -> row number of the first appended row.  normalize=False takes the rows as they are and checks
+        max|x| <= 1 (one host read; add is not the latency path)."""
+        if not torch.is_tensor(embeddings) or embeddings.dim() != 2 or embeddings.shape[1] != self.dim:
+            raise ValueError("GalleryIndex.add: expected a [n, %d] tensor" % self.dim)
+        n = embeddings.shape[0]
+        has = pids is not None
+        if self._has_pids is not None and has != self._has_pids:
+            raise ValueError("GalleryIndex.add: pids must be given on every add or on none")
+        if has:
+            pids = torch.as_tensor(pids)
+            if pids.numel() != n:
+                raise ValueError("GalleryIndex.add: %d pids for %d rows" % (pids.numel(), n))
+        first = self._n
+        if first + n > MAX_ROWS:
+            raise ValueError("GalleryIndex.add: at most %d rows (2**21 - 1: the 31-bit offsets of the P16 retrieval kernels); %d + %d asked" % (MAX_ROWS, first, n))
+        x = self._check_rows("add", embeddings)
+        if n == 0:
+            return first
+        if not normalize:
+            biggest = float(ops.amax(x).item())
+            if not biggest <= 1.0:
+                raise ValueError("GalleryIndex.add(normalize=False): rows must satisfy max|x| <= 1 (the fixed unit scale); got %g" % biggest)
+        self._reserve(first + n, x.device)
+        dst = self._rows[first : first + n]
+        if normalize:
+            inv = ops.empty((n,), x)
+            call("trid_l2norm_rows_f32", _p(x), _p(dst), _p(inv), n, self.dim, 1e-12, stream())
+        else:
+            dst.copy_(x)
+        self._pack_into(first, n)
+        if has:
+            self._pids[first : first + n].copy_(pids.to(x.device).long().reshape(-1))
+        self._has_pids = has
+        self._n = first + n
+        return first
+
+    # ------------------------------------------------------------------ search
+    def _workspace(self, nbytes):
+        """ONE cached buffer: the query panel (P16 [32, 256]), the normalised queries ([32, 256] fp32), their inverse norms and
+        the workers' lists - allocated on first use (and after a growth), zero-filled so that the panel's padding rows are zero"""
+        head = 2 * SMALL_Q * self.dim * 4 + 256
+        ws = self._ws.get("small")
+        if ws is None or ws.numel() < head + nbytes:
+            ws = torch.zeros(head + max(nbytes, 16), dtype=torch.uint8, device=self._rows.device)
+            self._ws["small"] = ws
+            self._panel_rows = 0
+        pb = SMALL_Q * self.dim * 4
+        q16 = ws[:pb].view(torch.float32).view(SMALL_Q, self.dim)
+        qn = ws[pb : 2 * pb].view(torch.float32).view(SMALL_Q, self.dim)
+        inv = ws[2 * pb : 2 * pb + SMALL_Q * 4].view(torch.float32)
+        return q16, qn, inv, ws[head:]
+
+    def _search_small(self, x, k, normalize, vals, rows, workgroups=0):
+        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read."""
+        Q, G = x.shape[0], self._n
+        L = ops.L.load()
+        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
+        q16, qn, inv, lists = self._workspace(need)
+        if normalize:
+            call("trid_l2norm_rows_f32", _p(x), _p(qn), _p(inv), Q, self.dim, 1e-12, stream())
+            x = qn
+        if Q < self._panel_rows:  # (rows a larger earlier batch left: the panel stays zero-padded)
+            q16[Q : self._panel_rows].zero_()
+        self._panel_rows = Q
+        call("trid_p16_pack_f32", _p(x), Q, self.dim, self.dim, _p(self._unit), _p(q16), 1, stream())
+        call("trid_index_search_p16", _p(q16), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+
+    def search(self, queries, k=10, normalize=True):
+        """-> (values [Q,k] f32, rows [Q,k] i64), value descending then row ascending.  Q <= 32: one pass of
+        trid_index_search_p16 (no host read, capturable with torch.cuda.graph); larger batches: the launch sequence of
+        similarity_topk on the index's own gallery operands.  normalize=False: the queries are unit rows already."""
+        if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError("GalleryIndex.search: expected a [Q, %d] tensor" % self.dim)
+        G = self._n
+        if G == 0:
+            raise ValueError("GalleryIndex.search: the index is empty")
+        if k < 1 or k > MAX_K or k > G:
+            raise ValueError("GalleryIndex.search: k must be in [1, %d] and <= len(index) = %d; got %d" % (MAX_K, G, k))
+        Q = queries.shape[0]
+        if Q == 0:
+            raise ValueError("GalleryIndex.search: no queries")
+        _need_cuda("search", queries)
+        x = queries.contiguous().float()
+        if x.device != self._rows.device:
+            raise ValueError("GalleryIndex.search: the index lives on %s; got queries on %s" % (self._rows.device, x.device))
+        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
+        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        if Q <= SMALL_Q:
+            self._search_small(x, k, normalize, vals, rows)
+            return vals, rows
+        from . import evaluation as E
+
+        q = ops.l2norm_rows(x)[0] if normalize else x
+        ws = ops.empty((ops.L.load().trid_topk_ws_floats(Q, G, k),), q)
+        E._sim_topk_call(q, self._rows[:G], vals, rows, k, 0, ws, g16=self._p16[:G], ga=self._unit)
+        return vals, rows
+
+    # ------------------------------------------------------------------ persistence
+    def state_dict(self):
+        """the normalised fp32 rows and the pids (None without); P16 is re-derived on load"""
+        return {"rows": None if self._rows is None else self._rows[: self._n].clone(),
+                "pids": None if not self._has_pids else self._pids[: self._n].clone()}
+
+    def load_state_dict(self, sd):
+        """Replace the contents.  The rows are taken as they are (already normalised: no second normalisation) and re-packed."""
+        rows = sd["rows"]
+        if rows is None or rows.shape[0] == 0:
+            self._n, self._has_pids = 0, None
+            return
+        if rows.shape[0] > MAX_ROWS:
+            raise ValueError("GalleryIndex.load_state_dict: at most %d rows; got %d" % (MAX_ROWS, rows.shape[0]))
+        x = self._check_rows("load_state_dict", rows)
+        n = x.shape[0]
+        self._n, self._has_pids = 0, None
+        self._reserve(n, x.device)
+        self._rows[:n].copy_(x)
+        self._pack_into(0, n)
+        pids = sd.get("pids")
+        self._has_pids = pids is not None
+        if pids is not None:
+            self._pids[:n].copy_(torch.as_tensor(pids).to(x.device).long().reshape(-1))
+        self._n = n

@@ -2,9 +2,85 @@
 the on-the-fly split GEMM; agreement of the results.  usage: python tools/retrieval_time.py [G] [Q] [--map]
 --map: times the matrix-free mAP (evaluation.rank_from_embeddings, 3 positives per query on synthetic pids; plain, and the re-ranked
 ranks with the gallery's neighbour lists given)
-next to the top-10 match at the same Q and G and prints one bench-line JSON with the rows/s figures and their ratios."""
+next to the top-10 match at the same Q and G and prints one bench-line JSON with the rows/s figures and their ratios.
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N]
+--index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
+after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
+embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
+median and the spread (min, max) of each in ms, the bytes the index search needs, the HBM floor they give at 6.3 TB/s, the one-off
+add time.  --wg N forces the number of workers of the one-pass kernel (tuning)."""
 import json, os, sys, time
 import torch
+
+
+def index_main(argv):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import textreid_amd.evaluation as E
+    from textreid_amd import GalleryIndex
+
+    wg = 0
+    if "--wg" in argv:
+        i = argv.index("--wg")
+        wg = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+    nums = [int(float(a)) for a in argv]
+    G = nums[0] if nums else 1000000
+    Qs = nums[1:] if len(nums) > 1 else [1, 8, 32, 64, 256]
+    CALLS, WARM, K, HBM = 20, 3, 10, 6.3e12
+    gen = torch.Generator(device="cpu").manual_seed(7)
+    g_raw = (torch.randn(G, 256, generator=gen) * 3.0).cuda()
+    idx = GalleryIndex(capacity=G)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    idx.add(g_raw)
+    torch.cuda.synchronize()
+    line = {"G": G, "C": 256, "k": K, "calls": CALLS, "warmup": WARM, "forced_workgroups": wg, "add_ms": (time.perf_counter() - t0) * 1e3, "Q": {}}
+    g_unit = idx.rows
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    for Q in Qs:
+        q_raw = (torch.randn(Q, 256, generator=gen) * 3.0).cuda()
+        q_unit = E.l2_normalize_rows(q_raw)
+        out_v = torch.empty(Q, K, device="cuda")
+        out_r = torch.empty(Q, K, dtype=torch.int64, device="cuda")
+        forms = {"index": (lambda: idx.search(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx._search_small(q_raw, K, True, out_v, out_r, wg)),
+                 "topk_raw": lambda: E.similarity_topk(q_raw, g_raw, K),
+                 "topk_unit": lambda: E.similarity_topk(q_unit, g_unit, K, normalize=False)}
+        for fn in forms.values():
+            for _ in range(WARM):
+                fn()
+        torch.cuda.synchronize()
+        times = {n: [] for n in forms}
+        for _ in range(CALLS):
+            for n, fn in forms.items():
+                times[n].append(timed(fn))
+        ent = {}
+        for n, ts in times.items():
+            ts = sorted(ts)
+            ent[n + "_ms"] = {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1]}
+        if Q <= 32:
+            lists = 2 * int(E.ops.L.load().trid_index_search_ws_bytes(G, Q, K, wg))  # written by the pass, read by the merge
+            ent["index_bytes"] = G * 1024 + 32 * 1024 + lists
+            ent["hbm_floor_ms"] = ent["index_bytes"] / HBM * 1e3
+            ent["index_over_floor"] = ent["index_ms"]["median"] / ent["hbm_floor_ms"]
+        ent["raw_over_index"] = ent["topk_raw_ms"]["median"] / ent["index_ms"]["median"]
+        ent["unit_over_index"] = ent["topk_unit_ms"]["median"] / ent["index_ms"]["median"]
+        a, b = idx.search(q_raw, K), E.similarity_topk(q_raw, g_raw, K)
+        ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
+        ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
+        line["Q"][str(Q)] = ent
+    print(json.dumps(line), flush=True)
+
+
+if "--index" in sys.argv:
+    index_main([a for a in sys.argv[1:] if a != "--index"])
+    sys.exit(0)
 MAP = "--map" in sys.argv
 sys.argv = [a for a in sys.argv if a != "--map"]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
