@@ -798,9 +798,14 @@ int trid_rank_metrics(const int64_t* indices, const int64_t* q_pids, const int64
  *   mode 1 (count): counts[e] += #{rows of g preceding pair e}, thresholds read from val; counts is zeroed by the caller,
  *     merged by integer atomics (run-to-run identical); max_list = the longest list of a query (a host value: the gallery
  *     streams once per 6 entries of it).  Nothing is stored per element.
- * offset: global index of g's row 0 (as trid_sim_topk_*).  CURRENTLY UNUSED beyond its check (>= 0): the listed rows and the
- * streamed rows belong to the same g, so the tie-break on offset + i is the local order i < j and the kernels compare local
- * rows.  It is the argument the sharded form (thresholds all-gathered with GLOBAL rows, counts summed) will compare against.
+ * offset: global index of g's row 0 (as trid_sim_topk_*): g is one SHARD of the gallery, rows offset .. offset + G - 1 of it,
+ * and idx holds GLOBAL rows, which may lie below, inside or above the shard.  The tie rule is on global rows: local row i
+ * precedes pair (t, j) iff s > t, or s == t and offset + i < j (the kernels reduce j once, in 64 bit, to the local comparison
+ * row clamp(j - offset, -1, G)).  Mode 1 adds this shard's share to counts: the thresholds of ALL listed pairs come from their
+ * owners (all-gathered / SUM-reduced by the caller) and the counts of the shards are summed.  Mode 0 of trid_rank_stream_f32
+ * writes val[e] only where offset <= idx[e] < offset + G and leaves the other entries untouched (a zero-filled val then SUM-
+ * reduces exactly); mode 0 of trid_rank_stream_p16 streams gathered rows and does not look at offset.  offset == 0 with every
+ * idx < G is the one-shard form.
  * Limits: a list passed to mode 0 of trid_rank_stream_p16 holds fewer than 2^21 pairs (the gathered rows stay below 2 GB;
  * the Python host chunks longer lists); trid_rank_stream_f32 needs the whole [Q, 8192] panel, it does not chunk over Q.
  * trid_rank_stream_p16: C == 256, operands pre-split (q16 = P16 [ceil32(Q)][256], padding rows zero; trid_p16_pack_f32) on the
@@ -824,6 +829,11 @@ int trid_rank_pairs_jaccard_f32(const int64_t* ptr, const int64_t* idx, float* v
 int trid_rank_rerank_fix(const int64_t* pos_ptr, const int64_t* pos_idx, const float* thr, int32_t* counts, const int64_t* nb_ptr,
                          const int64_t* nb_idx, const float* nb_val, const int64_t* qnn, const int64_t* gnn, int n, float alpha,
                          int Q, long long NB, void* stream);
+/* ... over one shard of the gallery (rows offset .. of the global one): nb_idx and gnn [G_local, n] are LOCAL rows of the shard,
+ * pos_idx GLOBAL rows, the two votes compare offset + i with j in 64 bit; counts take this shard's share. */
+int trid_rank_rerank_fix_shard(const int64_t* pos_ptr, const int64_t* pos_idx, const float* thr, int32_t* counts, const int64_t* nb_ptr,
+                               const int64_t* nb_idx, const float* nb_val, const int64_t* qnn, const int64_t* gnn, int n, float alpha,
+                               int Q, long long NB, long long offset, void* stream);
 /* counts [NP] (= rank - 1) -> first_hit[q] = the smallest (INT_MAX without relevant rows), ap[q] = (1/P) sum_k k / r_(k) over the
  * query's ranks in ascending order (NaN when P == 0), cmc[t] = 100*mean(first_hit < topk[t]), any topk (evaluation.py:20-36) */
 int trid_rank_finalize(const int32_t* counts, const int64_t* ptr, int Q, int32_t* first_hit, float* ap, const int64_t* topk,

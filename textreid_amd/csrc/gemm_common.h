@@ -28,11 +28,12 @@ struct GemmFilter {
 constexpr int RANK_PC = 6;
 struct RankCount {
     const long long* ptr;  // [Q + 1] CSR over the queries
-    const long long* idx;  // [NP] streamed-row index of each listed pair
+    const long long* idx;  // [NP] GLOBAL row of each listed pair (the streamed rows are rows offset .. offset + M - 1)
     float* val;            // [NP] pair_mode: written (the pair's own value); else read (thresholds)
     int* counts;           // [NP] += (integer atomics)
     int p0;                // this pass counts entries p0 .. p0 + RANK_PC - 1 of every query's list
     int pair_mode;         // 1: the streamed rows ARE the listed rows, gathered in CSR order; row r's value goes to val[r]
+    long long offset;      // global row of streamed row 0: a listed row j is compared as clamp(j - offset, -1, M) (count mode)
 };
 
 // Eval-mode epilogues (BatchNorm of running statistics, ReLU, residual fused into the convolution: m_resnet.py:54-67 under

@@ -241,7 +241,10 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
             const int e = r_lo + p.rk.p0 + u;
             const bool ok = !p.rk.pair_mode && e < r_hi;
             const float tu = ok ? p.rk.val[e] : INFINITY;
-            const int ju = ok ? (int)p.rk.idx[e] : -1;
+            // (the listed row, GLOBAL, as a row of this shard: one below it never wins a tie, one above it always does)
+            long long jl = ok ? p.rk.idx[e] - p.rk.offset : -1ll;
+            jl = jl < -1ll ? -1ll : jl > (long long)p.M ? (long long)p.M : jl;
+            const int ju = (int)jl;
             if (khalf == 0) {
                 lds_store1u(r_lds + 4u * u, __float_as_uint(tu));
                 lds_store1u(r_lds + 4u * (RPCN + u), (unsigned)ju);

@@ -9,6 +9,8 @@
 //   3. re-rank: s' = s + alpha J(nn(q), nn(i)) differs from s on the pairs with intersecting neighbour sets only, so the
 //      streamed pass counts against the re-ranked thresholds and a correction over those pairs moves the few counts;
 //   4. finalise (retrieval.hip, beside cmc_kernel): one wave per query orders its ranks by enumeration and sums the precision terms.
+// Sharded gallery: g is rows offset .. offset + G - 1 of the global one and the lists name GLOBAL rows; a shard counts its own rows
+// against the thresholds of all pairs with the tie rule on offset + i, and the shards' counts are summed by the caller.
 
 #include "gemm_common.h"
 
@@ -45,8 +47,9 @@ __device__ __forceinline__ float jaccard_term(const long long* __restrict__ a, c
 
 }  // namespace
 
-// generic path, pair values: the listed pairs whose row lies in the panel's columns [c0, c0 + n) take their value from it
-__global__ __launch_bounds__(256) void rank_pick_panel_kernel(const float* __restrict__ panel, int ld, int n, int c0,
+// generic path, pair values: the listed pairs whose (global) row lies in the panel's columns [c0, c0 + n) - c0 = the shard's
+// offset + the panel's first local row - take their value from it; the others are left as they are
+__global__ __launch_bounds__(256) void rank_pick_panel_kernel(const float* __restrict__ panel, int ld, int n, long long c0,
                                                               const long long* __restrict__ ptr, const long long* __restrict__ idx,
                                                               float* __restrict__ val, int Q, long long NP) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(256) void rank_pick_panel_kernel(const float* __res
 // generic path, count: one workgroup per query walks its panel row once per RANK_PC listed positives
 __global__ __launch_bounds__(256) void rank_count_panel_kernel(const float* __restrict__ panel, int ld, int n, int c0,
                                                                const long long* __restrict__ ptr, const long long* __restrict__ idx,
-                                                               const float* __restrict__ thr, int* __restrict__ counts) {
+                                                               const float* __restrict__ thr, int* __restrict__ counts, long long offset) {
     const int q = blockIdx.x, lane = threadIdx.x & 63;
     const int b = (int)ptr[q], e = (int)ptr[q + 1];
     const float* r = panel + (long long)q * ld;
@@ -70,7 +73,10 @@ __global__ __launch_bounds__(256) void rank_count_panel_kernel(const float* __re
         for (int u = 0; u < RANK_PC; ++u) {
             const bool ok = p0 + u < e;
             t[u] = ok ? thr[p0 + u] : INFINITY;
-            j[u] = ok ? (int)idx[p0 + u] : -1;
+            // (the listed row, GLOBAL, as a column of this panel: one below it never wins a tie, one beyond it always does)
+            long long jl = ok ? idx[p0 + u] - offset - c0 : -1ll;
+            jl = jl < -1ll ? -1ll : jl > (long long)n ? (long long)n : jl;
+            j[u] = (int)jl;
             c[u] = 0;
             tmin = fminf(tmin, t[u]);
         }
@@ -78,7 +84,7 @@ __global__ __launch_bounds__(256) void rank_count_panel_kernel(const float* __re
             const float v = r[i];
             if (v >= tmin) {
 #pragma unroll
-                for (int u = 0; u < RANK_PC; ++u) c[u] += precedes(v, c0 + i, t[u], j[u]);
+                for (int u = 0; u < RANK_PC; ++u) c[u] += precedes(v, i, t[u], j[u]);
             }
         }
 #pragma unroll
@@ -121,6 +127,30 @@ __global__ __launch_bounds__(256) void rank_rerank_fix_kernel(const long long* _
     }
 }
 
+// ... over one shard of the gallery: nb_idx and gnn are LOCAL rows of the shard whose row 0 is global row `offset`, pos_idx are
+// GLOBAL rows (any shard's); counts are this shard's share, summed over the shards afterwards
+__global__ __launch_bounds__(256) void rank_rerank_fix_shard_kernel(const long long* __restrict__ pos_ptr, const long long* __restrict__ pos_idx,
+                                                                    const float* __restrict__ thr, int* __restrict__ counts,
+                                                                    const long long* __restrict__ nb_ptr, const long long* __restrict__ nb_idx,
+                                                                    const float* __restrict__ nb_val, const long long* __restrict__ qnn,
+                                                                    const long long* __restrict__ gnn, int n, float alpha, int Q, long long NB,
+                                                                    long long offset) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NB) return;
+    const int q = csr_row(nb_ptr, Q, e);
+    const long long i = nb_idx[e];
+    const float v = nb_val[e];
+    const float v2 = __fadd_rn(v, jaccard_term(qnn + (long long)q * n, gnn + i * n, n, alpha));
+    if (v2 == v) return;
+    const long long gi = offset + i;
+    for (long long p = pos_ptr[q]; p < pos_ptr[q + 1]; ++p) {
+        const float t = thr[p];
+        const bool first = gi < pos_idx[p];
+        const int d = ((v2 > t || (v2 == t && first)) ? 1 : 0) - ((v > t || (v == t && first)) ? 1 : 0);
+        if (d != 0) atomicAdd(counts + p, d);
+    }
+}
+
 }  // namespace trid
 
 using namespace trid;
@@ -133,7 +163,7 @@ extern "C" long long trid_rank_ws_floats(int Q, int G) { return (long long)Q * r
     TRID_REQUIRE(ptr && idx && val && Q > 0 && G > 0 && NP >= 0 && NP < (1ll << 31), name ": null list or bad sizes (Q=%d G=%d NP=%lld)", Q, G, NP); \
     TRID_REQUIRE(mode == 0 || mode == 1, name ": mode must be 0 (pair values) or 1 (count)");                                    \
     TRID_REQUIRE(mode == 0 || (counts && max_list >= 0), name ": the count pass needs counts and the longest list's length");   \
-    /* (offset: checked and otherwise unused - one shard's tie-break on offset + i is the local order; see the header) */         \
+    /* (offset: the global row of the streamed g's row 0; idx holds global rows - see the header) */                              \
     TRID_REQUIRE(offset >= 0, name ": negative row offset")
 
 extern "C" int trid_rank_stream_p16(const void* q16, const void* a16, const float* q_amax, const float* g_amax, const int64_t* ptr,
@@ -146,7 +176,7 @@ extern "C" int trid_rank_stream_p16(const void* q16, const void* a16, const floa
     if (NP == 0) return TRID_OK;
     RankCount rk;
     rk.ptr = (const long long*)ptr; rk.idx = (const long long*)idx; rk.val = val; rk.counts = counts;
-    rk.p0 = 0; rk.pair_mode = mode == 0;
+    rk.p0 = 0; rk.pair_mode = mode == 0; rk.offset = offset;
     if (mode == 0) return stream_rank_count(a16, g_amax, q16, q_amax, G, Q, rk, (hipStream_t)stream);
     for (int p0 = 0; p0 < max_list; p0 += RANK_PC) {  // (queries whose list ends before p0 drop out at the first comparison)
         rk.p0 = p0;
@@ -179,11 +209,11 @@ extern "C" int trid_rank_stream_f32(const float* q, const float* g, const int64_
         int rc = trid_gemm_launch(&d, nullptr, nullptr, stream);
         if (rc) return rc;
         if (mode == 0)
-            hipLaunchKernelGGL(rank_pick_panel_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, stream, (const float*)ws, Gc, n, c0,
+            hipLaunchKernelGGL(rank_pick_panel_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, stream, (const float*)ws, Gc, n, offset + c0,
                                (const long long*)ptr, (const long long*)idx, val, Q, NP);
         else
             hipLaunchKernelGGL(rank_count_panel_kernel, dim3(Q), dim3(256), 0, stream, (const float*)ws, Gc, n, c0, (const long long*)ptr,
-                               (const long long*)idx, (const float*)val, counts);
+                               (const long long*)idx, (const float*)val, counts, offset);
         rc = check_launch("trid_rank_stream_f32");
         if (rc) return rc;
     }
@@ -211,4 +241,17 @@ extern "C" int trid_rank_rerank_fix(const int64_t* pos_ptr, const int64_t* pos_i
                        (const long long*)pos_idx, thr, counts, (const long long*)nb_ptr, (const long long*)nb_idx, nb_val, (const long long*)qnn,
                        (const long long*)gnn, n, alpha, Q, NB);
     return check_launch("trid_rank_rerank_fix");
+}
+
+extern "C" int trid_rank_rerank_fix_shard(const int64_t* pos_ptr, const int64_t* pos_idx, const float* thr, int32_t* counts,
+                                          const int64_t* nb_ptr, const int64_t* nb_idx, const float* nb_val, const int64_t* qnn,
+                                          const int64_t* gnn, int n, float alpha, int Q, long long NB, long long offset, void* stream) {
+    TRID_REQUIRE(pos_ptr && pos_idx && thr && counts && nb_ptr && nb_idx && nb_val && qnn && gnn && Q > 0 && NB >= 0 && NB < (1ll << 31),
+                 "trid_rank_rerank_fix_shard: null operand or bad sizes");
+    TRID_REQUIRE(n >= 1 && n <= 8 && alpha >= 0.f && offset >= 0, "trid_rank_rerank_fix_shard: 1 <= n <= 8 neighbours, alpha >= 0, offset >= 0");
+    if (NB == 0) return TRID_OK;
+    hipLaunchKernelGGL(rank_rerank_fix_shard_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)pos_ptr, (const long long*)pos_idx, thr, counts, (const long long*)nb_ptr, (const long long*)nb_idx,
+                       nb_val, (const long long*)qnn, (const long long*)gnn, n, alpha, Q, NB, offset);
+    return check_launch("trid_rank_rerank_fix_shard");
 }

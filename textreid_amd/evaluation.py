@@ -7,6 +7,9 @@ output_folder, topk, save_data, rerank)`` (:76-173) incl. the k-reciprocal / Jac
 fused form for large galleries (config 5): the [Q,G] matrix is never kept, only
 per-query top-k (value, index) pairs; with ``world_size > 1`` the gallery is
 sharded by rows and the per-shard top-k lists are merged after one all-gather.
+``positive_ranks`` / ``rank_from_embeddings`` / ``evaluation(matrix_free=True)`` give
+CMC at any k and mAP without the [Q,G] matrix on one rank; the ``*_sharded`` functions
+are their explicitly collective forms over a gallery sharded the same way.
 """
 
 import logging
@@ -224,19 +227,27 @@ def _neighbour_list(qnn, gnn):
     return _csr(rid // n, order[ent] // n, Q, G)
 
 
+def _p16_path(prec, C, G):
+    """the case the streaming P16 kernels take (as _sim_topk_call): fp16-split default arithmetic, C == 256, more rows than the
+    first panel, 31-bit offsets"""
+    return USE_SIM_P16 and prec == 16 and C == 256 and G > 8192 and G * 1024 < (1 << 31)
+
+
 PAIR_CHUNK = 1 << 18  # listed pairs per pair-value launch of the streaming kernel (256 MB of gathered gallery rows)
 
 
 class _RankOperands:
     """q and g as the rank passes take them: pre-split once for the streaming kernel (the case _sim_topk_call runs on it), else
-    the fp32 rows and ONE [Q, 8192] panel."""
+    the fp32 rows and ONE [Q, 8192] panel.  The sharded form hands in what it decided over ALL shards: ga (the GLOBAL gallery
+    amax the local rows are packed with), p16 (the path) and offset (the global index of g's row 0)."""
 
-    def __init__(self, q, g):
+    def __init__(self, q, g, ga=None, p16=None, offset=0):
         self.q, self.g = q, g
         self.Q, self.C = q.shape
         self.G = g.shape[0]
-        self.prec, self.qa, self.ga = _sim_precision(q, g)
-        self.p16 = USE_SIM_P16 and self.prec == 16 and self.C == 256 and self.G > 8192 and self.G * 1024 < (1 << 31)
+        self.offset = offset
+        self.prec, self.qa, self.ga = _sim_precision(q, g, ga)
+        self.p16 = _p16_path(self.prec, self.C, self.G) if p16 is None else p16
         if self.p16:
             self.q16 = torch.zeros((self.Q + 31) // 32 * 32, self.C, dtype=torch.float32, device=q.device)
             call("trid_p16_pack_f32", _p(q), self.Q, self.C, self.C, _p(self.qa), _p(self.q16), 1, stream())
@@ -245,10 +256,13 @@ class _RankOperands:
         else:
             self.ws = ops.empty((ops.L.load().trid_rank_ws_floats(self.Q, self.G),), q)
 
-    def run(self, ptr, idx, val, counts, max_list, mode):
+    def run(self, ptr, idx, val, counts, max_list, mode, local=False):
+        """idx: GLOBAL rows in mode 1; mode 0 takes rows of THIS g (local=True when g is a shard: the pairs it owns, its
+        neighbour list)"""
         NP = idx.numel()
         if NP == 0:
             return
+        offset = 0 if local else self.offset
         if self.p16 and mode == 0:
             # pair values: the listed rows are gathered and stream through the counting tile code, PAIR_CHUNK entries at a time
             # (the gathered copy stays small; the kernel's 31-bit offsets allow 2^21 rows): entries a .. b - 1 with the CSR
@@ -261,10 +275,10 @@ class _RankOperands:
                      b - a, b - a, 0, 0, 0, stream())
         elif self.p16:
             call("trid_rank_stream_p16", _p(self.q16), _p(self.g16), _p(self.qa), _p(self.ga), _p(ptr), _p(idx), _p(val), _p(counts), self.Q,
-                 self.G, NP, max_list, 0, 1, stream())
+                 self.G, NP, max_list, offset, 1, stream())
         else:
             call("trid_rank_stream_f32", _p(self.q), _p(self.g), _p(ptr), _p(idx), _p(val), _p(counts), self.Q, self.G, self.C, NP, max_list,
-                 0, self.prec, _p(self.qa), _p(self.ga), _p(self.ws), mode, stream())
+                 offset, self.prec, _p(self.qa), _p(self.ga), _p(self.ws), mode, stream())
 
 
 def _positive_counts(q, g, q_pids, g_pids, qnn, gnn, alpha):
@@ -332,6 +346,234 @@ def rank_from_embeddings(text_embed, image_embed, q_pids, g_pids, topk=(1, 5, 10
     mAP = torch.empty(1, dtype=torch.float32, device=dev)
     ops.sum_to(ap, mAP, 100.0 / Q)
     return cmc, mAP[0]
+
+
+# ---- the sharded form: the gallery split by rows over the ranks (rank-major global order, as similarity_topk takes it), the
+# queries replicated.  Explicitly collective: EVERY rank calls these (the unsharded entry points above keep refusing under a
+# process group - engine.inference calls evaluation on rank 0 alone).  DESIGN.md section 7e.
+
+GNN_ROWS = 8192  # gallery rows (all ranks together) scored per step of the gallery x gallery neighbour match
+
+
+def _refuse_sharded(name, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("textreid_amd.evaluation.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("textreid_amd.evaluation.%s reads list lengths back to the host and cannot run inside a stream capture" % name)
+
+
+def _owner_split(ptr, idx, offset, G_local):
+    """the entries of a CSR list of GLOBAL rows that lie in the shard [offset, offset + G_local): (ptr of the sub-list [Q+1], their
+    LOCAL rows, their positions in the full list) - device bookkeeping, no host loop"""
+    own = (idx >= offset) & (idx < offset + G_local)
+    before = torch.cat([own.new_zeros(1, dtype=torch.int64), torch.cumsum(own.long(), 0)])  # owned entries before entry e
+    pos = own.nonzero().reshape(-1)
+    return before[ptr].contiguous(), (idx[pos] - offset).contiguous(), pos
+
+
+class _Shards:
+    """What every rank decides alike before the first pass: the shard sizes, this shard's offset, the GLOBAL gallery amax and
+    the path; then this rank's operands (None for an empty shard: it joins the collectives and launches no rank kernel)."""
+
+    def __init__(self, q, g):
+        from .parallel import group_gather_rows, rank as dist_rank
+
+        self.q, self.g = q, g
+        self.Q, self.C = q.shape
+        self.G_local = g.shape[0]
+        dev = q.device
+        self.sizes = [int(v) for v in group_gather_rows(torch.tensor([self.G_local], dtype=torch.int64, device=dev)).tolist()]
+        self.W, self.r = len(self.sizes), (dist_rank() if len(self.sizes) > 1 else 0)
+        self.offset, self.G = sum(self.sizes[: self.r]), sum(self.sizes)
+        # ONE scale for every shard: each product then has the bits it has in the one-rank run
+        ga = None
+        if ops.GEMM_PRECISION == 6 and ops.CONV_PRECISION == 16:  # (the fp16-split default of _sim_precision: it takes the scalars)
+            mine = ops.amax(g) if self.G_local else torch.zeros(1, dtype=torch.float32, device=dev)
+            ga = group_gather_rows(mine.reshape(1)).max().reshape(1)
+        # ONE path: the streaming kernel only if every non-empty shard qualifies (two arithmetics would break "a row compares
+        # equal to its own duplicate" across a cut)
+        self.p16 = ga is not None and all(_p16_path(16, self.C, n) for n in self.sizes if n)
+        self.opnd = _RankOperands(q, g, ga, self.p16, self.offset) if self.G_local else None
+        self.ga = ga
+
+    def gather_gallery(self, x):
+        from .parallel import group_gather_varrows
+
+        return group_gather_varrows(x, self.sizes)
+
+    def topk(self, qrows, qa, k):
+        """global top-k rows [Qn, k] of replicated query rows against the sharded gallery: this shard's list with the operands
+        packed once (offset -> global rows), the lists of all shards merged (ties: lower global row first).  The launch sequence
+        of _sim_topk_call with what that decides per call - the path from the local G, the query scale from the rows passed -
+        fixed by the caller for all shards"""
+        from .parallel import group_gather_rows
+
+        Qn, dev = qrows.shape[0], qrows.device
+        vals = torch.full((Qn, k), float("-inf"), dtype=torch.float32, device=dev)
+        idx = torch.zeros(Qn, k, dtype=torch.int64, device=dev)
+        o = self.opnd
+        if o is not None:
+            kk = min(k, o.G)
+            v, i = (vals, idx) if kk == k else (torch.empty(Qn, kk, dtype=torch.float32, device=dev), torch.empty(Qn, kk, dtype=torch.int64, device=dev))
+            ws = ops.empty((ops.L.load().trid_topk_ws_floats(Qn, o.G, kk),), qrows)
+            if self.p16:
+                q16 = torch.zeros((Qn + 31) // 32 * 32, self.C, dtype=torch.float32, device=dev)
+                call("trid_p16_pack_f32", _p(qrows), Qn, self.C, self.C, _p(qa), _p(q16), 1, stream())
+                args = (_p(qrows), _p(o.g), _p(q16), _p(o.g16), _p(v), _p(i), Qn, o.G, kk, self.offset, _p(qa), _p(o.ga), _p(ws))
+                call("trid_sim_topk_p16", *args, 1, stream())
+                flag = ws[ops.L.load().trid_topk_ws_flag_offset(Qn, o.G):][:1].view(torch.int32)
+                if int(flag.item()) != 0:  # (a candidate list overflowed: the dense passes, as _sim_topk_call)
+                    call("trid_sim_topk_p16", *args, 2, stream())
+            else:
+                call("trid_sim_topk_f32", _p(qrows), _p(o.g), _p(v), _p(i), Qn, o.G, self.C, kk, self.offset, o.prec, _p(qa), _p(o.ga), _p(ws), stream())
+            if kk != k:
+                vals[:, :kk], idx[:, :kk] = v, i
+        if self.W == 1:
+            return idx
+        W = self.W
+        cand_v = group_gather_rows(vals).view(W, Qn, k).permute(1, 0, 2).reshape(Qn, W * k).contiguous()
+        cand_i = group_gather_rows(idx).view(W, Qn, k).permute(1, 0, 2).reshape(Qn, W * k).contiguous()
+        sel = torch.empty(Qn, k, dtype=torch.int64, device=dev)
+        call("trid_topk_rows_f32", _p(cand_v), W * k, Qn, W * k, k, _p(vals), _p(sel), stream())
+        return torch.gather(cand_i, 1, sel)
+
+    def neighbours(self, n):
+        """(qnn [Q, n], gnn_local [G_local, n]), GLOBAL rows: the queries' and this shard's rows' nearest gallery rows.  The
+        gallery x gallery match goes GNN_ROWS rows at a time (every rank's next rows, all-gathered): nothing grows with
+        G_total x 8192"""
+        from .parallel import group_gather_rows
+
+        if self.G < n:
+            raise ValueError("the re-rank needs at least neighbor_num gallery rows")
+        dev = self.q.device
+        qa = self.opnd.qa if self.opnd is not None else (ops.amax(self.q) if self.ga is not None else None)
+        qnn = self.topk(self.q, qa, n)
+        gnn = torch.empty(self.G_local, n, dtype=torch.int64, device=dev)
+        ch = max(256, GNN_ROWS // self.W)
+        for c0 in range(0, max(self.sizes), ch):
+            m = min(max(self.G_local - c0, 0), ch)
+            rows = torch.zeros(ch, self.C, dtype=torch.float32, device=dev)
+            rows[:m] = self.g[c0:c0 + m]
+            idx = self.topk(group_gather_rows(rows), self.ga, n)  # (gallery rows as queries: the gallery's scale)
+            gnn[c0:c0 + m] = idx[self.r * ch:self.r * ch + m]
+        return qnn, gnn
+
+
+def _positive_counts_sharded(sh, q_pids, g_pids_local, qnn, gnn_local, alpha):
+    from .parallel import group_reduce_sum_
+
+    dev = sh.q.device
+    Q = sh.Q
+    # the global list, identical on every rank
+    ptr, idx = _positive_list(q_pids, sh.gather_gallery(g_pids_local.to(dev).long()))
+    NP = idx.numel()
+    counts = torch.zeros(max(NP, 1), dtype=torch.int32, device=dev)
+    thr = torch.zeros(max(NP, 1), dtype=torch.float32, device=dev)
+    if NP == 0:
+        return ptr, idx, counts[:0]
+    max_list = int((ptr[1:] - ptr[:-1]).max())
+    o = sh.opnd
+    if qnn is not None:
+        n = qnn.shape[1]
+        qnn = qnn.long().contiguous()
+        gnn_local = gnn_local.long().contiguous()
+    # pair values: the owner of a row computes its entries (with the re-rank: plus their Jaccard term, from its own gnn rows);
+    # the others leave +0.0 there, so the SUM is exact
+    if o is not None:
+        own_ptr, own_idx, own_pos = _owner_split(ptr, idx, sh.offset, sh.G_local)
+        if own_pos.numel():
+            own_val = torch.empty(own_pos.numel(), dtype=torch.float32, device=dev)
+            o.run(own_ptr, own_idx, own_val, None, 0, 0, local=True)
+            if qnn is not None:
+                call("trid_rank_pairs_jaccard_f32", _p(own_ptr), _p(own_idx), _p(own_val), _p(qnn), _p(gnn_local), n, float(alpha), Q,
+                     own_pos.numel(), stream())
+            thr[own_pos] = own_val
+    group_reduce_sum_(thr)
+    # this shard's share of every count: the global list, the reduced thresholds, the tie rule on offset + i
+    if o is not None:
+        o.run(ptr, idx, thr, counts, max_list, 1)
+        if qnn is not None:
+            nb_ptr, nb_idx = _neighbour_list(qnn, gnn_local)  # (pairs (q, LOCAL row i))
+            NB = nb_idx.numel()
+            if NB:
+                nb_val = torch.empty(NB, dtype=torch.float32, device=dev)
+                o.run(nb_ptr, nb_idx, nb_val, None, 0, 0, local=True)
+                call("trid_rank_rerank_fix_shard", _p(ptr), _p(idx), _p(thr), _p(counts), _p(nb_ptr), _p(nb_idx), _p(nb_val), _p(qnn),
+                     _p(gnn_local), n, float(alpha), Q, NB, sh.offset, stream())
+    group_reduce_sum_(counts)
+    return ptr, idx, counts
+
+
+def _sharded_rows(x, normalize):
+    if normalize and x.shape[0]:
+        return l2_normalize_rows(x)
+    return x.contiguous().float()
+
+
+def positive_ranks_sharded(q, g_local, q_pids, g_pids_local, qnn=None, gnn_local=None, alpha=0.05, normalize=False):
+    """positive_ranks over a gallery sharded by rows: COLLECTIVE over the default process group (every rank calls it; one rank:
+    the unsharded result).  q, q_pids (and qnn) are replicated; g_local, g_pids_local (and gnn_local, rows of GLOBAL neighbour
+    indices) are this rank's rows, rank-major global order; shard sizes may differ and may be 0.
+    -> (pos_ptr [Q+1], pos_idx [NP] GLOBAL rows, ranks [NP]), identical on every rank"""
+    _refuse_sharded("positive_ranks_sharded", q, g_local)
+    if (qnn is None) != (gnn_local is None):
+        raise ValueError("positive_ranks_sharded: qnn and gnn_local go together")
+    sh = _Shards(_sharded_rows(q, normalize), _sharded_rows(g_local, normalize))
+    ptr, idx, counts = _positive_counts_sharded(sh, q_pids, g_pids_local, qnn, gnn_local, alpha)
+    return ptr, idx, counts.long() + 1
+
+
+def rank_from_embeddings_sharded(text_embed, image_embed_local, q_pids, g_pids_local, topk=(1, 5, 10), get_mAP=True, normalize=True,
+                                 rerank=False, neighbor_num=5, alpha=0.05):
+    """rank_from_embeddings over a gallery sharded by rows (layout and collectivity as positive_ranks_sharded); the neighbour
+    lists of the re-rank come from the sharded top-k.  -> (cmc, mAP) or (cmc,), identical on every rank"""
+    _refuse_sharded("rank_from_embeddings_sharded", text_embed, image_embed_local)
+    dev = text_embed.device
+    sh = _Shards(_sharded_rows(text_embed, normalize), _sharded_rows(image_embed_local, normalize))
+    qnn, gnn = sh.neighbours(neighbor_num) if rerank else (None, None)
+    ptr, idx, counts = _positive_counts_sharded(sh, q_pids, g_pids_local, qnn, gnn, alpha)
+    Q = sh.Q
+    topk_t = torch.as_tensor(topk, dtype=torch.int64, device=dev)
+    first = torch.empty(Q, dtype=torch.int32, device=dev)
+    ap = torch.empty(Q, dtype=torch.float32, device=dev)
+    cmc = torch.empty(topk_t.numel(), dtype=torch.float32, device=dev)
+    call("trid_rank_finalize", _p(counts), _p(ptr), Q, _p(first), _p(ap), _p(topk_t), topk_t.numel(), _p(cmc), stream())
+    if not get_mAP:
+        return (cmc,)
+    mAP = torch.empty(1, dtype=torch.float32, device=dev)
+    ops.sum_to(ap, mAP, 100.0 / Q)
+    return cmc, mAP[0]
+
+
+def tables_sharded(image_local, image_pid_local, text_local, text_pid_local, topk=(1, 5, 10), rerank=True):
+    """The tables evaluation(matrix_free=True) leaves in evaluation.last_results, from L2-normalised image and text rows that
+    are BOTH sharded over the ranks (collective): per direction the query side is all-gathered and replicated, the gallery side
+    stays sharded.  -> {"t2i", "i2t"[, "re-t2i", "re-i2t"]: (cmc, mAP or None)}"""
+    from .parallel import group_gather_rows, group_gather_varrows
+
+    _refuse_sharded("tables_sharded", image_local, text_local)
+    dev = image_local.device
+
+    def whole(x):
+        sizes = [int(v) for v in group_gather_rows(torch.tensor([x.shape[0]], dtype=torch.int64, device=dev)).tolist()]
+        return group_gather_varrows(x.contiguous(), sizes)
+
+    image_local, text_local = image_local.contiguous().float(), text_local.contiguous().float()
+    image_pid_local, text_pid_local = image_pid_local.to(dev).long(), text_pid_local.to(dev).long()
+    image_all, image_pid_all = whole(image_local), whole(image_pid_local)
+    text_all, text_pid_all = whole(text_local), whole(text_pid_local)
+
+    def table(q, g, qp, gp, re):
+        r = rank_from_embeddings_sharded(q, g, qp, gp, topk, get_mAP=rerank, normalize=False, rerank=re)
+        return (r[0], r[1] if rerank else None)
+
+    results = {}
+    for re in ((False, True) if rerank else (False,)):
+        pre = "re-" if re else ""
+        results[pre + "i2t"] = table(image_all, text_local, image_pid_all, text_pid_local, re)
+        results[pre + "t2i"] = table(text_all, image_local, text_pid_all, image_pid_local, re)
+    return results
 
 
 def _evaluation_matrix_free(dataset, predictions, output_folder, topk, save_data, rerank, logger):

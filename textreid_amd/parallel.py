@@ -158,6 +158,33 @@ def _all_reduce_sum_impl(t):
     return dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=True)
 
 
+# ---- the explicitly collective evaluation forms (evaluation.*_sharded): every rank calls them; without a process group (one
+# rank) each helper is the identity, so the sharded form of one rank is the unsharded computation
+def group_gather_rows(x):
+    """all_gather_rows over the default group; x itself without one"""
+    return all_gather_rows(x) if dp_active() else x.contiguous()
+
+
+def group_gather_varrows(x, sizes):
+    """[sizes[rank], ...] per rank (sizes: the host list every rank holds, zeros allowed) -> [sum(sizes), ...] rank-major"""
+    if not dp_active():
+        return x.contiguous()
+    n = max(max(sizes), 1)
+    pad = torch.zeros((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    pad[: x.shape[0]] = x
+    rows = all_gather_rows(pad).view((len(sizes), n) + tuple(x.shape[1:]))
+    return torch.cat([rows[w, :s] for w, s in enumerate(sizes)], dim=0).contiguous()
+
+
+def group_reduce_sum_(t):
+    """in-place SUM all-reduce over the default group, complete on return; nothing without one"""
+    if dp_active():
+        w = _all_reduce_sum_impl(t)
+        if w is not None:
+            w.wait()
+    return t
+
+
 def broadcast_module_state(module, src=0):
     """Every parameter and buffer of `module` from rank `src` to all ranks, once (what DistributedDataParallel does when it
     wraps the model: train_net.py:50-56 - with `broadcast_buffers=False` the buffers are synchronised at construction only).

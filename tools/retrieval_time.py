@@ -3,6 +3,10 @@ the on-the-fly split GEMM; agreement of the results.  usage: python tools/retrie
 --map: times the matrix-free mAP (evaluation.rank_from_embeddings, 3 positives per query on synthetic pids; plain, and the re-ranked
 ranks with the gallery's neighbour lists given)
 next to the top-10 match at the same Q and G and prints one bench-line JSON with the rows/s figures and their ratios.
+Under torch.distributed.run with more than one rank --map times the SHARDED form instead (evaluation.rank_from_embeddings_sharded /
+positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
+them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
+usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
 usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
@@ -78,8 +82,47 @@ def index_main(argv):
     print(json.dumps(line), flush=True)
 
 
+def map_sharded_main(argv):
+    import torch.distributed as dist
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import textreid_amd.evaluation as E
+
+    nums = [int(float(a)) for a in argv]
+    G = nums[0] if nums else 1000000
+    Q = nums[1] if len(nums) > 1 else 10000
+    r, W = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    ndev = torch.cuda.device_count()
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", r)) % ndev)
+    dist.init_process_group(os.environ.get("TRID_DIST_BACKEND", "nccl" if ndev >= W else "gloo"), init_method="env://")
+    gen = torch.Generator(device="cpu").manual_seed(7)  # (the inputs of the one-rank run, cut by rows)
+    q = torch.nn.functional.normalize(torch.randn(Q, 256, generator=gen), dim=1).cuda()
+    lo, hi = r * G // W, (r + 1) * G // W
+    g = torch.nn.functional.normalize(torch.randn(G, 256, generator=gen), dim=1)[lo:hi].cuda()
+    qp = torch.arange(Q, device="cuda")
+    gp = (torch.arange(G, device="cuda") % max(G // 3, 1))[lo:hi].contiguous()
+    gnn = ((torch.arange(lo, hi, device="cuda").view(-1, 1) + torch.arange(5, device="cuda").view(1, -1) * 7919) % G).contiguous()
+    line = {"world": W, "backend": dist.get_backend(), "devices": ndev, "Q": Q, "G": G, "C": 256, "positives_per_query": 3}
+
+    def rerank_leg():
+        return E.positive_ranks_sharded(q, g, qp, gp, E.similarity_topk(q, g, 5, normalize=False)[1], gnn, 0.05)
+    for name, fn in (("map", lambda: E.rank_from_embeddings_sharded(q, g, qp, gp, (1, 5, 10), normalize=False)), ("map_rerank", rerank_leg)):
+        fn(); torch.cuda.synchronize(); dist.barrier()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize(); dist.barrier()
+        line[name + "_rows_per_s"] = G / ((time.perf_counter() - t0) / 3)
+    if r == 0:
+        print(json.dumps(line), flush=True)
+    dist.destroy_process_group()
+
+
 if "--index" in sys.argv:
     index_main([a for a in sys.argv[1:] if a != "--index"])
+    sys.exit(0)
+if "--map" in sys.argv and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    map_sharded_main([a for a in sys.argv[1:] if a != "--map"])
     sys.exit(0)
 MAP = "--map" in sys.argv
 sys.argv = [a for a in sys.argv if a != "--map"]
