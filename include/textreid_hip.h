@@ -772,6 +772,19 @@ long long trid_topk_ws_flag_offset(int Q, int G);
 long long trid_index_search_ws_bytes(int G, int Q, int k, int workgroups);
 int trid_index_search_p16(const void* q16, const void* g16, const float* unit_amax, int Q, int G, int k,
                           long long idx_offset, float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream);
+/* The same search restricted to ALLOWED rows (row removal and filtered search of GalleryIndex): mask_words = uint32 [ceil(G / 32)]
+ * on the device, 4-byte aligned; bit (r & 31) of word (r >> 5) set = row r may be returned (bits of rows >= G are ignored).  The bit
+ * is applied in the selection step of the same kernel, before the running threshold sees a value: a disallowed row is never a
+ * candidate and never tightens the threshold, so the result is the exact top-k of the allowed rows.  Everything else - arithmetic,
+ * order, limits (k <= G included), ws - as trid_index_search_p16.  A query with fewer than k allowed rows gets its real results
+ * first, then (-inf, -1) slots (-1 whatever idx_offset).  No host read: the mask's contents are an input like the queries. */
+int trid_index_search_masked_p16(const void* q16, const void* g16, const float* unit_amax, const uint32_t* mask_words, int Q, int G,
+                                 int k, long long idx_offset, float* out_val, int64_t* out_idx, void* ws, int workgroups,
+                                 void* stream);
+/* The mask words of the search above from byte arrays: words[w] bit b = live[32 w + b] != 0 && allow[32 w + b] != 0 for rows < n,
+ * 0 for rows >= n.  live / allow: uint8 [n] on the device; either may be NULL (it then counts as all ones), not both.
+ * n_words >= ceil(n / 32); EVERY word up to n_words is written.  No host read, no allocation. */
+int trid_index_pack_mask_u32(const uint8_t* live, const uint8_t* allow, int n, uint32_t* words, int n_words, void* stream);
 
 /* per-row top-k of a given similarity matrix (rank(get_mAP=False), evaluation.py:17-19) */
 int trid_topk_rows_f32(const float* sim, int ld, int Q, int G, int k, float* out_val, int64_t* out_idx,

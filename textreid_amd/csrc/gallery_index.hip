@@ -10,11 +10,15 @@
 //   * selection needs no earlier pass: a lane keeps a running threshold of its query (from -inf), appends the rare elements above
 //     it to a lane-private staging list in LDS and folds the list into a sorted list of 16 in registers when it fills;
 //   * a workgroup leaves one sorted list of k per query; a second launch merges the workgroups' lists.
+// index_search_kernel<true> (trid_index_search_masked_p16) also honours a per-row ALLOW bit: a wave's 32 rows of a step tile are one
+// 32-bit mask word, read on the scalar path; a row whose bit is clear becomes -inf BEFORE the selection sees it, so it is never
+// staged and never tightens the threshold.  trid_index_pack_mask_u32 derives the words from byte arrays (liveness, caller's mask).
 // Arithmetic and product order are those of gemm_p16_kernel<A_KC> (hi*lo + lo*hi + hi*hi per 16-deep k step, k ascending, gallery
 // = A, queries = B): the similarities are bit-identical to trid_gemm_p16 on the same operands.
 // ONE order everywhere: value descending, then gallery row ascending - the result does not depend on the partition.
 
 #include <algorithm>
+#include <cstdio>
 #include <mutex>
 
 #include "split_common.h"
@@ -63,7 +67,9 @@ __device__ __forceinline__ bool ix_before(float av, int ar, float bv, int br) { 
 
 }  // namespace
 
-__global__ __launch_bounds__(IX_NW * 64) void index_search_kernel(IxParams p) {
+// MASKED: mask = uint32[ceil(G / 32)], bit (r & 31) of word (r >> 5) set = row r may be returned (unused and NULL otherwise)
+template <bool MASKED>
+__global__ __launch_bounds__(IX_NW * 64) void index_search_kernel(IxParams p, const unsigned* __restrict__ mask) {
     constexpr int KG = 8;
     extern __shared__ __attribute__((aligned(16))) uint4 ix_smem[];
     char* const lds = reinterpret_cast<char*>(ix_smem);
@@ -175,6 +181,14 @@ __global__ __launch_bounds__(IX_NW * 64) void index_search_kernel(IxParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         int zero = 0;
         asm volatile("" : "+v"(zero));
+        // this wave's 32 rows are ONE mask word, the same for every lane: a scalar load (it counts on lgkmcnt, not on the vmcnt that
+        // orders the ring), issued BEFORE the DMA of tile t + 1 so that it neither queues behind those 32 KB nor is waited for
+        // before they are under way (a wave without rows in a ragged last tile has no word)
+        unsigned mw = 0xFFFFFFFFu;
+        if constexpr (MASKED) {
+            const int word = t * IX_NW + wave;
+            mw = word * 32 < p.G ? mask[word] : 0u;
+        }
         // the other slot was last read by the MFMAs of tile t - 1, all issued: free
         if (t + 1 < t1) issue(t + 1, slot ^ 1, zero);
 
@@ -207,6 +221,24 @@ __global__ __launch_bounds__(IX_NW * 64) void index_search_kernel(IxParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (rb + (r & 3) + 8 * (r >> 2) >= p.G) acc[r] = -INFINITY;
+        }
+        if constexpr (MASKED) {
+            // The allow bits come BEFORE the maximum and the threshold: a disallowed row becomes -inf, so it is never staged and never
+            // moves f_thr.  Element r is row 4 khalf + (r & 3) + 8 (r >> 2) of the wave's 32: the lanes of k half 0 look at bit
+            // b = (r & 3) + 8 (r >> 2) of the word, those of k half 1 at bit b + 4 - a 64-bit LANE mask formed on the scalar unit
+            // (two sign-extended 1-bit fields), one v_cndmask per element (the compiler's own form tests the bit per lane: 3 VALU)
+            if (mw != 0xFFFFFFFFu) {
+                const float ninf = -INFINITY;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int b = (r & 3) + 8 * (r >> 2);
+                    const unsigned lo = (unsigned)((int)(mw << (31 - b)) >> 31), hi = (unsigned)((int)(mw << (27 - b)) >> 31);
+                    const unsigned long long keep = ((unsigned long long)hi << 32) | lo;
+                    float a = acc[r];
+                    asm("v_cndmask_b32_e64 %0, %1, %0, %2" : "+v"(a) : "v"(ninf), "s"(keep));
+                    acc[r] = a;
+                }
+            }
         }
         float mx = acc[0];
 #pragma unroll
@@ -293,6 +325,19 @@ __global__ __launch_bounds__(256) void index_merge_kernel(const float* __restric
     }
 }
 
+// words[w] bit b = live[32 w + b] && allow[32 w + b] for rows < n (a NULL array counts as all ones), 0 beyond: one ballot per 64 rows
+__global__ __launch_bounds__(256) void index_pack_mask_kernel(const uint8_t* __restrict__ live, const uint8_t* __restrict__ allow, int n,
+                                                              unsigned* __restrict__ words, int n_words) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool on = row < n;
+    if (on && live != nullptr) on = live[row] != 0;
+    if (on && allow != nullptr) on = allow[row] != 0;
+    const unsigned long long b = __ballot(on);
+    const int lane = threadIdx.x & 63;
+    const long long w = (row >> 6) * 2 + (lane >> 5);
+    if ((lane & 31) == 0 && w < n_words) words[w] = lane ? (unsigned)(b >> 32) : (unsigned)b;
+}
+
 static int ix_workers(int G, int workgroups) {
     if (workgroups > 0) return workgroups;
     const int tiles = (G + IX_RB - 1) / IX_RB;
@@ -308,21 +353,24 @@ extern "C" long long trid_index_search_ws_bytes(int G, int Q, int k, int workgro
     return (long long)ix_workers(G, workgroups) * Q * k * 8;
 }
 
-extern "C" int trid_index_search_p16(const void* q16, const void* g16, const float* unit_amax, int Q, int G, int k, long long idx_offset,
-                                     float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream) {
-    TRID_REQUIRE(q16 && g16 && unit_amax && out_val && out_idx && ws, "trid_index_search_p16: null operand");
-    TRID_REQUIRE(Q >= 1 && Q <= 32, "trid_index_search_p16: 1 <= Q <= 32 (Q=%d): larger batches go through trid_sim_topk_p16", Q);
-    TRID_REQUIRE(G >= 1 && (long long)G * IX_ROWB < (1ll << 31), "trid_index_search_p16: 1 <= G and G * 1024 < 2^31 (G=%d)", G);
-    TRID_REQUIRE(k >= 1 && k <= TOPK_MAX && k <= G, "trid_index_search_p16: k must be in [1,%d] and <= G (k=%d G=%d)", TOPK_MAX, k, G);
-    TRID_REQUIRE(workgroups >= 0 && workgroups <= IX_MAX_WORKERS, "trid_index_search_p16: 0 <= workgroups <= %d (workgroups=%d)", IX_MAX_WORKERS, workgroups);
-    TRID_REQUIRE(aligned16(q16) && aligned16(g16) && aligned16(ws), "trid_index_search_p16: operands must be 16-byte aligned");
-    static std::once_flag once;
+template <bool MASKED>
+static int ix_search(const char* fn, const void* q16, const void* g16, const float* unit_amax, const uint32_t* mask_words, int Q, int G, int k,
+                     long long idx_offset, float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream) {
+    TRID_REQUIRE(q16 && g16 && unit_amax && out_val && out_idx && ws, "%s: null operand", fn);
+    if (MASKED) TRID_REQUIRE(mask_words != nullptr, "%s: null mask_words (the unmasked search is trid_index_search_p16)", fn);
+    TRID_REQUIRE(Q >= 1 && Q <= 32, "%s: 1 <= Q <= 32 (Q=%d): larger batches go through trid_sim_topk_p16", fn, Q);
+    TRID_REQUIRE(G >= 1 && (long long)G * IX_ROWB < (1ll << 31), "%s: 1 <= G and G * 1024 < 2^31 (G=%d)", fn, G);
+    TRID_REQUIRE(k >= 1 && k <= TOPK_MAX && k <= G, "%s: k must be in [1,%d] and <= G (k=%d G=%d)", fn, TOPK_MAX, k, G);
+    TRID_REQUIRE(workgroups >= 0 && workgroups <= IX_MAX_WORKERS, "%s: 0 <= workgroups <= %d (workgroups=%d)", fn, IX_MAX_WORKERS, workgroups);
+    TRID_REQUIRE(aligned16(q16) && aligned16(g16) && aligned16(ws), "%s: operands must be 16-byte aligned", fn);
+    if (MASKED) TRID_REQUIRE((reinterpret_cast<uintptr_t>(mask_words) & 3u) == 0, "%s: mask_words must be 4-byte aligned", fn);
+    static std::once_flag once;  // (one per instantiation)
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)index_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_err = hipFuncSetAttribute((const void*)index_search_kernel<MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     if (attr_err != hipSuccess) {
-        set_error("trid_index_search_p16: cannot reserve LDS: %s", hipGetErrorString(attr_err));
+        set_error("%s: cannot reserve LDS: %s", fn, hipGetErrorString(attr_err));
         return (int)attr_err;
     }
     IxParams p;
@@ -333,9 +381,34 @@ extern "C" int trid_index_search_p16(const void* q16, const void* g16, const flo
     p.wval = reinterpret_cast<float*>(ws);
     p.wrow = reinterpret_cast<int*>(p.wval + (long long)p.W * Q * k);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(index_search_kernel, dim3(p.W), dim3(IX_NW * 64), IX_LDS, s, p);
-    int rc = check_launch("trid_index_search_p16");
+    hipLaunchKernelGGL(index_search_kernel<MASKED>, dim3(p.W), dim3(IX_NW * 64), IX_LDS, s, p, reinterpret_cast<const unsigned*>(mask_words));
+    char what[80];
+    int rc = check_launch(fn);
     if (rc != TRID_OK) return rc;
     hipLaunchKernelGGL(index_merge_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, p.wval, p.wrow, Q, p.W * k, k, idx_offset, out_val, reinterpret_cast<long long*>(out_idx));
-    return check_launch("trid_index_search_p16 (merge)");
+    snprintf(what, sizeof what, "%s (merge)", fn);
+    return check_launch(what);
+}
+
+extern "C" int trid_index_search_p16(const void* q16, const void* g16, const float* unit_amax, int Q, int G, int k, long long idx_offset,
+                                     float* out_val, int64_t* out_idx, void* ws, int workgroups, void* stream) {
+    return ix_search<false>("trid_index_search_p16", q16, g16, unit_amax, nullptr, Q, G, k, idx_offset, out_val, out_idx, ws, workgroups, stream);
+}
+
+extern "C" int trid_index_search_masked_p16(const void* q16, const void* g16, const float* unit_amax, const uint32_t* mask_words, int Q, int G,
+                                            int k, long long idx_offset, float* out_val, int64_t* out_idx, void* ws, int workgroups,
+                                            void* stream) {
+    return ix_search<true>("trid_index_search_masked_p16", q16, g16, unit_amax, mask_words, Q, G, k, idx_offset, out_val, out_idx, ws, workgroups,
+                           stream);
+}
+
+extern "C" int trid_index_pack_mask_u32(const uint8_t* live, const uint8_t* allow, int n, uint32_t* words, int n_words, void* stream) {
+    TRID_REQUIRE(live || allow, "trid_index_pack_mask_u32: live and allow are both NULL (one may be: it counts as all ones)");
+    TRID_REQUIRE(words != nullptr, "trid_index_pack_mask_u32: null words");
+    TRID_REQUIRE((reinterpret_cast<uintptr_t>(words) & 3u) == 0, "trid_index_pack_mask_u32: words must be 4-byte aligned");
+    TRID_REQUIRE(n >= 1, "trid_index_pack_mask_u32: n >= 1 (n=%d)", n);
+    TRID_REQUIRE((long long)n_words * 32 >= n && n_words <= (1 << 26), "trid_index_pack_mask_u32: ceil(n / 32) <= n_words <= 2^26 (n=%d n_words=%d)", n, n_words);
+    const int blocks = (int)(((long long)n_words * 32 + 255) / 256);
+    hipLaunchKernelGGL(index_pack_mask_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, live, allow, n, reinterpret_cast<unsigned*>(words), n_words);
+    return check_launch("trid_index_pack_mask_u32");
 }

@@ -11,12 +11,31 @@ Larger batches run the launch sequence of ``similarity_topk`` on the operands th
 
 Order of the results: value descending, then row number ascending (row number = insertion order).
 
-An index is used from ONE stream: ``add`` and ``search`` run on torch's current stream and share the cached workspace.  A
-recorded search answers against the gallery as it stood at the capture (row count and storage are part of the recording):
-record again after an ``add``.
+Removal and filtered search are ONE mechanism: a per-row allow bit that the one-pass kernel honours in its selection step, before
+the running threshold sees a value (``trid_index_search_masked_p16``) - a row that may not be returned is never a candidate and
+never tightens the threshold, so the answer is the exact top-k of the allowed rows.
+  * ``remove(rows=... | pids=...)`` marks rows as removed (tombstones) in a device liveness array, the single source of truth; the
+    packed mask words (one uint32 per 32 rows) are derived from it by ``trid_index_pack_mask_u32`` and cached until the next
+    ``add`` / ``remove`` / growth.  Row numbers never change: insertion order, stable across ``add`` and ``remove``; ``len``,
+    ``rows``, ``rows_p16``, ``pids`` and ``capacity`` include removed rows, ``live`` / ``live_count`` tell them apart.
+  * ``search(..., mask=m)``: ``m`` is a bool / uint8 tensor of length ``len`` on the index's device, true = the row may be returned;
+    the effective allow set is ``live & m``.  The mask's CONTENTS are an input like the queries: it is packed on the device on
+    every call (no host read), and a recorded search replays against whatever the tensor holds at replay time.
+  * k: with tombstones only, ``k <= live_count`` (the host knows the count; ValueError otherwise).  With a ``mask`` nothing is read
+    back: a query with fewer than k allowed rows gets its real results first, then ``(-inf, -1)`` slots.
+  * More than 32 queries with tombstones or a mask run in panels of 32 through the masked one-pass kernel, one gallery pass per
+    panel, written into slices of the outputs: exact, but one pass per 32 queries is slower per query than the unmasked large-batch
+    route (G = 1e6, Q = 256: 2.45 against 0.52 ms) - bulk callers ``compact()`` first.
+  * ``compact()`` drops the removed rows (stable order, P16 rows copied: they carry the fixed unit scale) and returns the old-row
+    -> new-row map; afterwards there are no tombstones and searches run the unmasked path again.
+An index that never saw ``remove`` and is searched without ``mask`` runs exactly the unmasked path (``trid_index_search_p16``).
 
-Not built: row removal, gallery shards over ranks, widths other than 256, an image-encoder convenience wrapper (``add`` takes
-embeddings, e.g. the image half of ``inference`` output).
+An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
+A recorded search answers against the gallery as it stood at the capture (row count, storage and tombstones are part of the
+recording): record again after ``add`` / ``remove`` / ``compact``.
+
+Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, top-k over distinct pids, an
+image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output).
 """
 
 import torch
@@ -50,6 +69,9 @@ class GalleryIndex:
         self._rows = None   # fp32 [capacity, 256], L2-normalised
         self._p16 = None    # the same rows, P16
         self._pids = None   # int64 [capacity] once pids were given
+        self._live = None   # bool [capacity]: False = removed (the single source of truth for tombstones)
+        self._dead = 0      # removed rows among the first len (host count)
+        self._words_ok = False  # the cached mask words of the tombstones are current
         self._has_pids = None
         self._unit = None   # device scalar 1.0: the amax every row and every query is packed with
         self._ws = {}       # the cached workspace of the small-batch search
@@ -85,6 +107,16 @@ class GalleryIndex:
     def pids(self):
         return None if not self._has_pids or self._pids is None else self._pids[: self._n]
 
+    @property
+    def live(self):
+        """bool [len]: False where the row was removed (a view of the storage)"""
+        return None if self._live is None else self._live[: self._n]
+
+    @property
+    def live_count(self):
+        """rows not removed (a host int)"""
+        return self._n - self._dead
+
     def _reserve(self, total, device):
         if self._rows is not None and self._rows.device != device:
             raise ValueError("GalleryIndex: the index lives on %s; got a tensor on %s" % (self._rows.device, device))
@@ -95,11 +127,14 @@ class GalleryIndex:
         rows = torch.empty(new_cap, self.dim, dtype=torch.float32, device=device)
         p16 = torch.empty(new_cap, self.dim, dtype=torch.float32, device=device)
         pids = torch.empty(new_cap, dtype=torch.int64, device=device)
+        live = torch.ones(new_cap, dtype=torch.bool, device=device)
         if self._n:
             rows[: self._n].copy_(self._rows[: self._n])
             p16[: self._n].copy_(self._p16[: self._n])
             pids[: self._n].copy_(self._pids[: self._n])
-        self._rows, self._p16, self._pids = rows, p16, pids
+            live[: self._n].copy_(self._live[: self._n])
+        self._rows, self._p16, self._pids, self._live = rows, p16, pids, live
+        self._words_ok = False
         if self._unit is None:
             self._unit = torch.ones(1, dtype=torch.float32, device=device)
 
@@ -147,8 +182,70 @@ class GalleryIndex:
         if has:
             self._pids[first : first + n].copy_(pids.to(x.device).long().reshape(-1))
         self._has_pids = has
+        self._live[first : first + n] = True
         self._n = first + n
+        self._words_ok = False
         return first
+
+    # ------------------------------------------------------------------ removal
+    def remove(self, rows=None, pids=None):
+        """Mark rows as removed; -> how many were newly removed.  Exactly one of ``rows`` (a list or an int64 tensor on any device;
+        a row outside [0, len) is a ValueError; duplicates and rows already removed are ignored) and ``pids`` (every row whose pid is
+        in the set).  Row numbers do not change.  One host read (the count): like add, not the latency path."""
+        if (rows is None) == (pids is None):
+            raise ValueError("GalleryIndex.remove: give exactly one of rows and pids")
+        n = self._n
+        if pids is not None:
+            if not self._has_pids:
+                raise ValueError("GalleryIndex.remove(pids=...): the index holds no pids")
+            want = torch.as_tensor(pids).to(self._rows.device).long().reshape(-1)
+            sel = torch.isin(self._pids[:n], want)
+        else:
+            if torch.is_tensor(rows) and rows.dtype != torch.int64:
+                raise ValueError("GalleryIndex.remove(rows=...): a list or an int64 tensor; got %s" % rows.dtype)
+            r = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+            if r.numel() == 0:
+                return 0
+            lo, hi = int(r.min()), int(r.max())
+            if lo < 0 or hi >= n:
+                raise ValueError("GalleryIndex.remove(rows=...): rows must be in [0, len(index) = %d); got %d" % (n, lo if lo < 0 else hi))
+            sel = torch.zeros(n, dtype=torch.bool, device=self._rows.device)
+            sel[r.to(self._rows.device)] = True
+        live = self._live[:n]
+        newly = int((sel & live).sum())
+        if newly:
+            live &= ~sel
+            self._dead += newly
+            self._words_ok = False
+        return newly
+
+    def compact(self):
+        """Drop the removed rows, order kept; -> int64 [old len] on the device, old row -> new row, -1 for a removed row.  Out of
+        place: rows, rows_p16 (copied, not re-packed: the fixed unit scale) and pids are gathered into new storage.  Afterwards
+        there are no tombstones and searches run the unmasked path; recorded searches must be recorded again."""
+        n = self._n
+        if self._rows is None:
+            return torch.empty(0, dtype=torch.int64)
+        dev = self._rows.device
+        if not self._dead:
+            return torch.arange(n, dtype=torch.int64, device=dev)
+        keep = torch.nonzero(self._live[:n]).reshape(-1)
+        m = keep.numel()
+        new_of = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        new_of[keep] = torch.arange(m, dtype=torch.int64, device=dev)
+        cap = max(m, 64)
+        rows = torch.empty(cap, self.dim, dtype=torch.float32, device=dev)
+        p16 = torch.empty(cap, self.dim, dtype=torch.float32, device=dev)
+        pids = torch.empty(cap, dtype=torch.int64, device=dev)
+        rows[:m] = self._rows[keep]
+        p16.view(torch.int32)[:m] = self._p16.view(torch.int32)[keep]
+        pids[:m] = self._pids[keep]
+        self._rows, self._p16, self._pids = rows, p16, pids
+        self._live = torch.ones(cap, dtype=torch.bool, device=dev)
+        self._n, self._dead, self._words_ok = m, 0, False
+        if m == 0:
+            self._has_pids = None
+        return new_of
 
     # ------------------------------------------------------------------ search
     def _workspace(self, nbytes):
@@ -166,8 +263,37 @@ class GalleryIndex:
         inv = ws[2 * pb : 2 * pb + SMALL_Q * 4].view(torch.float32)
         return q16, qn, inv, ws[head:]
 
-    def _search_small(self, x, k, normalize, vals, rows, workgroups=0):
-        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read."""
+    def _word_buffer(self, name):
+        """a cached uint32 buffer of one mask word per 32 rows of the CAPACITY: part of the index workspace, allocated on first use
+        and after a growth (outside any capture, as the workspace above)"""
+        nw = (self.capacity + 31) // 32
+        buf = self._ws.get(name)
+        if buf is None or buf.numel() < nw:
+            buf = torch.zeros(nw, dtype=torch.int32, device=self._rows.device)
+            self._ws[name] = buf
+            if name == "words_live":
+                self._words_ok = False
+        return buf
+
+    def _mask_words(self, mask):
+        """-> the packed allow words of ``live & mask`` (mask None: the tombstones alone, cached until add / remove / growth).  A
+        mask is packed on every call: its contents are an input."""
+        n = self._n
+        if mask is None:
+            if self._words_ok:  # (the latency path: nothing to derive, nothing to launch)
+                return self._ws["words_live"]
+            words = self._word_buffer("words_live")
+            if not self._words_ok:
+                call("trid_index_pack_mask_u32", _p(self._live), None, n, _p(words), words.numel(), stream())
+                self._words_ok = True
+            return words
+        words = self._word_buffer("words_mask")
+        call("trid_index_pack_mask_u32", _p(self._live) if self._dead else None, _p(mask), n, _p(words), words.numel(), stream())
+        return words
+
+    def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None):
+        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read.
+        words: the packed allow bits (the masked kernel); None: every row may be returned."""
         Q, G = x.shape[0], self._n
         L = ops.L.load()
         need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
@@ -179,12 +305,20 @@ class GalleryIndex:
             q16[Q : self._panel_rows].zero_()
         self._panel_rows = Q
         call("trid_p16_pack_f32", _p(x), Q, self.dim, self.dim, _p(self._unit), _p(q16), 1, stream())
-        call("trid_index_search_p16", _p(q16), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+        if words is None:
+            call("trid_index_search_p16", _p(q16), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+        else:
+            call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
 
-    def search(self, queries, k=10, normalize=True):
+    def search(self, queries, k=10, normalize=True, mask=None):
         """-> (values [Q,k] f32, rows [Q,k] i64), value descending then row ascending.  Q <= 32: one pass of
         trid_index_search_p16 (no host read, capturable with torch.cuda.graph); larger batches: the launch sequence of
-        similarity_topk on the index's own gallery operands.  normalize=False: the queries are unit rows already."""
+        similarity_topk on the index's own gallery operands.  normalize=False: the queries are unit rows already.
+        mask: bool / uint8 [len] on the index's device, true = the row may be returned; the allow set is ``live & mask``.  With
+        removed rows or a mask the search runs trid_index_search_masked_p16 (still no host read, still capturable: the mask's
+        contents are read at replay time; the tombstones are part of the recording - record again after add / remove / compact),
+        in panels of 32 queries when Q > 32 (one gallery pass per panel: compact() before bulk queries).  Removed rows only:
+        k <= live_count.  With a mask: a query with fewer than k allowed rows ends in (-inf, -1) slots."""
         if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError("GalleryIndex.search: expected a [Q, %d] tensor" % self.dim)
         G = self._n
@@ -192,6 +326,13 @@ class GalleryIndex:
             raise ValueError("GalleryIndex.search: the index is empty")
         if k < 1 or k > MAX_K or k > G:
             raise ValueError("GalleryIndex.search: k must be in [1, %d] and <= len(index) = %d; got %d" % (MAX_K, G, k))
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("GalleryIndex.search: mask must be a bool or uint8 tensor; got %s" % (mask.dtype if torch.is_tensor(mask) else type(mask)))
+            if mask.dim() != 1 or mask.shape[0] != G:
+                raise ValueError("GalleryIndex.search: mask must have shape [len(index) = %d]; got %s" % (G, tuple(mask.shape)))
+        elif k > self.live_count:
+            raise ValueError("GalleryIndex.search: k must be <= live_count = %d (%d of %d rows were removed); got %d" % (self.live_count, self._dead, G, k))
         Q = queries.shape[0]
         if Q == 0:
             raise ValueError("GalleryIndex.search: no queries")
@@ -199,8 +340,18 @@ class GalleryIndex:
         x = queries.contiguous().float()
         if x.device != self._rows.device:
             raise ValueError("GalleryIndex.search: the index lives on %s; got queries on %s" % (self._rows.device, x.device))
+        if mask is not None and mask.device != self._rows.device:
+            raise ValueError("GalleryIndex.search: the index lives on %s; got a mask on %s" % (self._rows.device, mask.device))
         vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
         rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        if mask is not None or self._dead:
+            words = self._mask_words(None if mask is None else mask.contiguous())
+            if Q <= SMALL_Q:
+                self._search_small(x, k, normalize, vals, rows, words=words)
+                return vals, rows
+            for at in range(0, Q, SMALL_Q):  # panels of 32 queries, one gallery pass each, into slices of the outputs
+                self._search_small(x[at : at + SMALL_Q], k, normalize, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], words=words)
+            return vals, rows
         if Q <= SMALL_Q:
             self._search_small(x, k, normalize, vals, rows)
             return vals, rows
@@ -213,21 +364,27 @@ class GalleryIndex:
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
-        """the normalised fp32 rows and the pids (None without); P16 is re-derived on load"""
+        """the normalised fp32 rows, the pids (None without) and the liveness (bool [len]; None when nothing was removed); P16 is
+        re-derived on load"""
         return {"rows": None if self._rows is None else self._rows[: self._n].clone(),
-                "pids": None if not self._has_pids else self._pids[: self._n].clone()}
+                "pids": None if not self._has_pids else self._pids[: self._n].clone(),
+                "live": None if not self._dead else self._live[: self._n].clone()}
 
     def load_state_dict(self, sd):
-        """Replace the contents.  The rows are taken as they are (already normalised: no second normalisation) and re-packed."""
+        """Replace the contents.  The rows are taken as they are (already normalised: no second normalisation) and re-packed.  A
+        state dict without "live" (as written before removal existed) loads as all-live."""
         rows = sd["rows"]
         if rows is None or rows.shape[0] == 0:
-            self._n, self._has_pids = 0, None
+            self._n, self._has_pids, self._dead, self._words_ok = 0, None, 0, False
             return
         if rows.shape[0] > MAX_ROWS:
             raise ValueError("GalleryIndex.load_state_dict: at most %d rows; got %d" % (MAX_ROWS, rows.shape[0]))
         x = self._check_rows("load_state_dict", rows)
         n = x.shape[0]
-        self._n, self._has_pids = 0, None
+        live = sd.get("live")
+        if live is not None and (not torch.is_tensor(live) or live.numel() != n):
+            raise ValueError("GalleryIndex.load_state_dict: live must hold one entry per row (%d)" % n)
+        self._n, self._has_pids, self._dead, self._words_ok = 0, None, 0, False
         self._reserve(n, x.device)
         self._rows[:n].copy_(x)
         self._pack_into(0, n)
@@ -235,4 +392,8 @@ class GalleryIndex:
         self._has_pids = pids is not None
         if pids is not None:
             self._pids[:n].copy_(torch.as_tensor(pids).to(x.device).long().reshape(-1))
+        self._live[:n] = True
+        if live is not None:
+            self._live[:n].copy_(live.to(x.device).reshape(-1) != 0)
+            self._dead = n - int(self._live[:n].sum())
         self._n = n

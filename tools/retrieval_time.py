@@ -7,12 +7,15 @@ Under torch.distributed.run with more than one rank --map times the SHARDED form
 positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
-usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N]
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
 median and the spread (min, max) of each in ms, the bytes the index search needs, the HBM floor they give at 6.3 TB/s, the one-off
-add time.  --wg N forces the number of workers of the one-pass kernel (tuning)."""
+add time.  --wg N forces the number of workers of the one-pass kernel (tuning).
+--masked [F]: a fourth form, index_masked, timed in the same process alternating with the others: the same search on a second index
+over the same gallery from which the fraction F (default 0.1) of the rows was removed (the masked one-pass kernel; panels of 32 queries
+for Q > 32).  Each Q entry gains index_masked_ms and masked_over_index = its median over the unmasked index search's median."""
 import json, os, sys, time
 import torch
 
@@ -27,6 +30,12 @@ def index_main(argv):
         i = argv.index("--wg")
         wg = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    masked = None
+    if "--masked" in argv:
+        i = argv.index("--masked")
+        given = i + 1 < len(argv) and 0.0 < float(argv[i + 1]) < 1.0  # (a fraction; an integer that follows is G or a Q)
+        masked = float(argv[i + 1]) if given else 0.1
+        argv = argv[:i] + argv[i + (2 if given else 1):]
     nums = [int(float(a)) for a in argv]
     G = nums[0] if nums else 1000000
     Qs = nums[1:] if len(nums) > 1 else [1, 8, 32, 64, 256]
@@ -40,6 +49,13 @@ def index_main(argv):
     torch.cuda.synchronize()
     line = {"G": G, "C": 256, "k": K, "calls": CALLS, "warmup": WARM, "forced_workgroups": wg, "add_ms": (time.perf_counter() - t0) * 1e3, "Q": {}}
     g_unit = idx.rows
+    idx_m = None
+    if masked is not None:
+        idx_m = GalleryIndex(capacity=G)
+        idx_m.add(g_raw)
+        gone = torch.nonzero(torch.rand(G, generator=gen) < masked).reshape(-1)
+        line["masked_fraction"], line["masked_removed"] = masked, idx_m.remove(rows=gone)
+        torch.cuda.synchronize()
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -56,6 +72,8 @@ def index_main(argv):
         forms = {"index": (lambda: idx.search(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx._search_small(q_raw, K, True, out_v, out_r, wg)),
                  "topk_raw": lambda: E.similarity_topk(q_raw, g_raw, K),
                  "topk_unit": lambda: E.similarity_topk(q_unit, g_unit, K, normalize=False)}
+        if idx_m is not None:
+            forms["index_masked"] = (lambda: idx_m.search(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx_m._search_small(q_raw, K, True, out_v, out_r, wg, idx_m._mask_words(None)))
         for fn in forms.values():
             for _ in range(WARM):
                 fn()
@@ -75,6 +93,9 @@ def index_main(argv):
             ent["index_over_floor"] = ent["index_ms"]["median"] / ent["hbm_floor_ms"]
         ent["raw_over_index"] = ent["topk_raw_ms"]["median"] / ent["index_ms"]["median"]
         ent["unit_over_index"] = ent["topk_unit_ms"]["median"] / ent["index_ms"]["median"]
+        if idx_m is not None:
+            ent["masked_over_index"] = ent["index_masked_ms"]["median"] / ent["index_ms"]["median"]
+            ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
         a, b = idx.search(q_raw, K), E.similarity_topk(q_raw, g_raw, K)
         ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
         ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
