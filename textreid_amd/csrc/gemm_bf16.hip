@@ -414,7 +414,7 @@ __global__ __launch_bounds__(NT, (BN == 64 && BMODE == B_KC && TRID_NARROW_WAVES
 
     // ---- epilogue (same contract as gemm.hip) -----------------------------------------
     if (F16) {  // undo the operand scales (exact: powers of two)
-        const float unscale = 1.f / (scaleA * scaleB);
+        const float unscale = f16_unscale_of(scaleA, scaleB);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll

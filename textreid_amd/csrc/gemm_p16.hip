@@ -521,7 +521,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4 && STAGES == 2) ? 2 : (W
     }
 
     // ---- epilogue (same contract as gemm_bf16.hip)
-    const float unscale = 1.f / (scaleA * scaleB);
+    const float unscale = f16_unscale_of(scaleA, scaleB);
     const int row_base = m0 + wm * (32 * TM) + 4 * khalf;
     const int col_base = n0 + wn * (32 * TN) + (lane & 31);
     unsigned short* __restrict__ Cb = reinterpret_cast<unsigned short*>(p.C);  // c_fmt 2: plain bf16 output (batch = splits = 1)
@@ -1213,7 +1213,7 @@ __global__ __launch_bounds__(512, 4) void gemm_p16_wgrad_kernel(GemmParams p) {
         }
     }
 
-    const float f = p.alpha / (scaleA * scaleB);
+    const float f = p.alpha * f16_unscale_of(scaleA, scaleB);
     const int row_base = m0 + wm * (32 * TM) + 4 * kh;
     const int col = n0 + wn * 32 + (lane & 31);
 #pragma unroll

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p16_stream_kernel(StreamParams p)
     const int n0 = panel * (CW * 32) + cw * 32;
     const bool col_live = n0 < p.N;  // (N % 32 == 0: a wave's 32 columns exist or do not)
 
-    const float unscale = 1.f / (f16_scale_of(*p.a_amax) * f16_scale_of(*p.b_amax));
+    const float unscale = f16_unscale_of(f16_scale_of(*p.a_amax), f16_scale_of(*p.b_amax));
 
     // ---- this wave's filter panel: [k group][k step][plane] fragments, K/2 VGPRs
     f16x8 bf[KG][2][2];

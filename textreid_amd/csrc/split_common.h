@@ -108,8 +108,15 @@ __device__ __forceinline__ float f16_scale_of(float amax) {
     const unsigned bits = __builtin_bit_cast(unsigned, amax);
     const int e = (int)((bits >> 23) & 0xffu);           // biased exponent of amax (floor(log2) + 127)
     if (e == 0 || e == 0xff) return 1.f;                 // zero / denormal / inf / nan: leave unscaled
-    return __builtin_bit_cast(float, (unsigned)(127 + 13 + 127 - e) << 23);  // 2^(13 - floor(log2 amax))
+    // 2^(13 - floor(log2 amax)), at most 2^127: for amax < 2^-114 (e <= 12) the exponent field would pass 254 - +inf at e = 12,
+    // the sign bit below that - and every consumer would turn zeros into NaN.  Such a tensor is scaled to below 2^13 instead
+    // (its largest element keeps the same 22 bits; the absolute floor of 2^-25 is still <= 2^-26 of the maximum at e = 1).
+    const int f = 127 + 13 + 127 - e;
+    return __builtin_bit_cast(float, (unsigned)(f < 254 ? f : 254) << 23);
 }
+// 1 / (sa * sb) for two of these scales, as the product of the reciprocals: the same bits wherever sa * sb is finite (powers of
+// two), and still the right power of two - a denormal at worst - where that product overflows (a 2^127 scale against any >= 2)
+__device__ __forceinline__ float f16_unscale_of(float sa, float sb) { return (1.f / sa) * (1.f / sb); }
 
 // two values -> (hi dword, lo dword) of packed fp16 pairs
 __device__ __forceinline__ void f16_split2(float x0, float x1, unsigned& hi, unsigned& lo) {

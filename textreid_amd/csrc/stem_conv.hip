@@ -151,7 +151,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_p16_kernel(HaloParams p) 
     const int W = p.W, H = p.H, TH = p.TH, R = p.R, rowb = p.rowb;
     const int cpr = rowb >> 10;  // DMA chunks per ring row
 
-    const float unscale = 1.f / (f16_scale_of(*p.x_amax) * f16_scale_of(*p.w_amax));
+    const float unscale = f16_unscale_of(f16_scale_of(*p.x_amax), f16_scale_of(*p.w_amax));
     // eval mode: this lane's channel coefficients, the output scale from the analytic bound
     float e_sc = 1.f, e_sh = 0.f, e_oscale = 1.f;
     unsigned e_tmax = 0;
@@ -799,7 +799,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_halo_p16_kernel(HaloWgra
     }
 
     // ---- the pixel groups of a (dy block, x block) pair meet in LDS, tap by tap; one slab per workgroup
-    const float f = 1.f / (f16_scale_of(*p.x_amax) * f16_scale_of(*p.dy_amax));
+    const float f = f16_unscale_of(f16_scale_of(*p.x_amax), f16_scale_of(*p.dy_amax));
     float* const tile = reinterpret_cast<float*>(smem);  // [NW][32][33]
     float* const out = p.slabs + (size_t)blockIdx.x * (COUT * 9 * CIN);
 #pragma unroll

@@ -154,8 +154,12 @@ extern "C" int trid_step_replay_build(void* graph_, int max_lanes, void** out) {
         }
         if (nd.type == hipGraphNodeTypeMemcpy) {
             // (this runtime returns nothing for the 1-D copy nodes a captured hipMemcpyAsync leaves: refuse rather than guess)
+            // (... or, seen on one box, fills the record with something that is no copy at all - a `kind` outside hipMemcpyKind,
+            // host-heap addresses as pointers -, which replayed as hipMemcpy3DAsync: invalid argument, with HIP's error left set)
             const hipMemcpy3DParms& c = nd.cp;
-            if (c.srcPtr.ptr == nullptr || c.dstPtr.ptr == nullptr || c.extent.width == 0) {
+            const bool kind_ok = c.kind == hipMemcpyHostToHost || c.kind == hipMemcpyHostToDevice || c.kind == hipMemcpyDeviceToHost ||
+                                 c.kind == hipMemcpyDeviceToDevice || c.kind == hipMemcpyDefault || c.kind == hipMemcpyDeviceToDeviceNoCU;
+            if (c.srcPtr.ptr == nullptr || c.dstPtr.ptr == nullptr || c.extent.width == 0 || !kind_ok) {
                 if (getenv("TRID_REPLAY_DEBUG")) {
                     for (int pass = 0; pass < 2; ++pass)
                         for (int q : (pass ? succs[i] : preds[i])) {
