@@ -140,5 +140,7 @@ int stream_rank_count(const void* a16, const float* a_amax, const void* q16, con
 int trid_gemm_launch(const trid_gemm_desc* d, const trid::GemmFilter* filt, const int* gate, hipStream_t stream);
 
 namespace trid {
-
+// columns of the [Q, Gc] similarity panel of the retrieval top-k and rank passes (retrieval.hip, rank_stream.hip): the whole
+// gallery up to 8192 rows (a multiple of 4), else 8192 at a time
+inline int chunk_cols(int G) { return G < 8192 ? ((G + 3) / 4 * 4) : 8192; }
 }  // namespace trid

@@ -106,29 +106,9 @@ __global__ __launch_bounds__(256) void rank_pairs_jaccard_kernel(const long long
 }
 
 // Re-rank correction.  counts came from the PLAIN similarities against the re-ranked thresholds; the pairs (q, i) of the
-// second list are the only ones whose value the Jaccard term moves: each takes its plain vote back and casts the moved one
-__global__ __launch_bounds__(256) void rank_rerank_fix_kernel(const long long* __restrict__ pos_ptr, const long long* __restrict__ pos_idx,
-                                                              const float* __restrict__ thr, int* __restrict__ counts,
-                                                              const long long* __restrict__ nb_ptr, const long long* __restrict__ nb_idx,
-                                                              const float* __restrict__ nb_val, const long long* __restrict__ qnn,
-                                                              const long long* __restrict__ gnn, int n, float alpha, int Q, long long NB) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= NB) return;
-    const int q = csr_row(nb_ptr, Q, e);
-    const int i = (int)nb_idx[e];
-    const float v = nb_val[e];
-    const float v2 = __fadd_rn(v, jaccard_term(qnn + (long long)q * n, gnn + (long long)i * n, n, alpha));
-    if (v2 == v) return;
-    for (long long p = pos_ptr[q]; p < pos_ptr[q + 1]; ++p) {
-        const float t = thr[p];
-        const int j = (int)pos_idx[p];
-        const int d = precedes(v2, i, t, j) - precedes(v, i, t, j);
-        if (d != 0) atomicAdd(counts + p, d);
-    }
-}
-
-// ... over one shard of the gallery: nb_idx and gnn are LOCAL rows of the shard whose row 0 is global row `offset`, pos_idx are
-// GLOBAL rows (any shard's); counts are this shard's share, summed over the shards afterwards
+// second list are the only ones whose value the Jaccard term moves: each takes its plain vote back and casts the moved one.
+// Over one shard of the gallery: nb_idx and gnn are LOCAL rows of the shard whose row 0 is global row `offset` (the whole gallery:
+// offset 0), pos_idx are GLOBAL rows (any shard's); counts are this shard's share, summed over the shards afterwards
 __global__ __launch_bounds__(256) void rank_rerank_fix_shard_kernel(const long long* __restrict__ pos_ptr, const long long* __restrict__ pos_idx,
                                                                     const float* __restrict__ thr, int* __restrict__ counts,
                                                                     const long long* __restrict__ nb_ptr, const long long* __restrict__ nb_idx,
@@ -155,9 +135,7 @@ __global__ __launch_bounds__(256) void rank_rerank_fix_shard_kernel(const long l
 
 using namespace trid;
 
-static int rank_chunk_cols(int G) { return G < 8192 ? ((G + 3) / 4 * 4) : 8192; }
-
-extern "C" long long trid_rank_ws_floats(int Q, int G) { return (long long)Q * rank_chunk_cols(G); }
+extern "C" long long trid_rank_ws_floats(int Q, int G) { return (long long)Q * chunk_cols(G); }
 
 #define RANK_LIST_OK(name)                                                                                                        \
     TRID_REQUIRE(ptr && idx && val && Q > 0 && G > 0 && NP >= 0 && NP < (1ll << 31), name ": null list or bad sizes (Q=%d G=%d NP=%lld)", Q, G, NP); \
@@ -194,7 +172,7 @@ extern "C" int trid_rank_stream_f32(const float* q, const float* g, const int64_
     if (NP == 0) return TRID_OK;
     hipStream_t stream = (hipStream_t)stream_;
     if (precision == 16 && !(q_amax && g_amax)) precision = 6;  // the fp16 split needs the operands' magnitudes
-    const int Gc = rank_chunk_cols(G);
+    const int Gc = chunk_cols(G);
     for (int c0 = 0; c0 < G; c0 += Gc) {  // one [Q, Gc] panel at a time
         const int n = (G - c0) < Gc ? (G - c0) : Gc;
         trid_gemm_desc d;
@@ -237,9 +215,9 @@ extern "C" int trid_rank_rerank_fix(const int64_t* pos_ptr, const int64_t* pos_i
                  "trid_rank_rerank_fix: null operand or bad sizes");
     TRID_REQUIRE(n >= 1 && n <= 8 && alpha >= 0.f, "trid_rank_rerank_fix: 1 <= n <= 8 neighbours, alpha >= 0");
     if (NB == 0) return TRID_OK;
-    hipLaunchKernelGGL(rank_rerank_fix_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)pos_ptr,
-                       (const long long*)pos_idx, thr, counts, (const long long*)nb_ptr, (const long long*)nb_idx, nb_val, (const long long*)qnn,
-                       (const long long*)gnn, n, alpha, Q, NB);
+    hipLaunchKernelGGL(rank_rerank_fix_shard_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)pos_ptr, (const long long*)pos_idx, thr, counts, (const long long*)nb_ptr, (const long long*)nb_idx,
+                       nb_val, (const long long*)qnn, (const long long*)gnn, n, alpha, Q, NB, 0ll);
     return check_launch("trid_rank_rerank_fix");
 }
 

@@ -237,11 +237,9 @@ __global__ __launch_bounds__(256) void jaccard_add_kernel(const long long* __res
 
 using namespace trid;
 
-static int topk_chunk_cols(int G) { return G < 8192 ? ((G + 3) / 4 * 4) : 8192; }
-
 // workspace: [Q x Gc similarity panel | later reused as Q candidate lists of Gc/2 (value, column) pairs]
 //            [Q list counters][1 overflow flag][copy of the running top-k after step 1: Q x k indices, Q x k values]
-static long long topk_ws_snap_offset(int Q, int G) { return ((long long)Q * topk_chunk_cols(G) + Q + 4 + 1) / 2 * 2; }
+static long long topk_ws_snap_offset(int Q, int G) { return ((long long)Q * chunk_cols(G) + Q + 4 + 1) / 2 * 2; }
 extern "C" long long trid_topk_ws_floats(int Q, int G, int k) {
     return topk_ws_snap_offset(Q, G) + 3ll * Q * k + 2;
 }
@@ -288,7 +286,7 @@ static int sim_topk(const float* q, const float* g, const void* q16, const void*
     TRID_REQUIRE(Q > 0 && G > 0 && C > 0 && C % 4 == 0, "trid_sim_topk_f32: bad shape (C%%4)");
     TRID_REQUIRE(k >= 1 && k <= TOPK_MAX && k <= G, "trid_sim_topk_f32: k must be in [1,%d] and <= G", TOPK_MAX);
     if (precision == 16 && !(q_amax && g_amax)) precision = 6;  // the fp16 split needs the operands' magnitudes
-    const int Gc = topk_chunk_cols(G);
+    const int Gc = chunk_cols(G);
     int* cnt = reinterpret_cast<int*>(ws + (long long)Q * Gc);
     int* overflow = cnt + Q;
     const int cap = Gc / 2;
@@ -402,7 +400,7 @@ static int sim_topk(const float* q, const float* g, const void* q16, const void*
     return TRID_OK;
 }
 
-extern "C" long long trid_topk_ws_flag_offset(int Q, int G) { return (long long)Q * topk_chunk_cols(G) + Q; }
+extern "C" long long trid_topk_ws_flag_offset(int Q, int G) { return (long long)Q * chunk_cols(G) + Q; }
 
 extern "C" int trid_sim_topk_f32(const float* q, const float* g, float* out_val, int64_t* out_idx, int Q, int G, int C,
                                  int k, long long idx_offset, int precision, const float* q_amax, const float* g_amax, float* ws,

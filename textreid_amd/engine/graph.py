@@ -126,6 +126,12 @@ class CapturedTrainStep:
             p.grad = None  # the captured backward allocates its gradients inside the graph's pool
         from .. import ops
 
+        # dead reference cycles go NOW: the ~1100 launches below allocate enough containers to start a full collection in the
+        # middle of the recording, and the destructor of an earlier recording's CUDAGraph synchronises the device - inside a
+        # capture that call fails in a destructor and ends the process (torch.cuda.graph collects only on request)
+        import gc
+
+        gc.collect()
         ops.begin_capture()
         torch.cuda.synchronize()
         g = None

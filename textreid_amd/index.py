@@ -7,7 +7,8 @@ pre-split (P16, include/textreid_hip.h "P16").  Unit rows satisfy ``|x| <= 1``, 
 ``amax = 1.0`` - one constant device scalar that is never recomputed: appending never re-packs earlier rows.  ``search`` with
 at most 32 queries is ONE pass over the P16 gallery (csrc/gallery_index.hip, ``trid_index_search_p16``): no host read, no
 allocation but the outputs and a workspace cached on the index, so it can be recorded with ``torch.cuda.graph`` and replayed.
-Larger batches run the launch sequence of ``similarity_topk`` on the operands the index already holds.
+Larger batches run the launch sequence of ``similarity_topk`` (``evaluation._Operands.topk``) with the index's own pre-split rows
+and unit scale handed in: nothing of the gallery is measured or packed.
 
 Order of the results: value descending, then row number ascending (row number = insertion order).
 
@@ -41,10 +42,11 @@ image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half
 import torch
 
 from . import ops
+from .evaluation import MAX_P16_ROWS, _Operands
 from .ops import _p, call, stream
 
 DIM = 256
-MAX_ROWS = (1 << 21) - 1  # the 31-bit byte offsets of the P16 retrieval kernels: rows * 1024 < 2^31
+MAX_ROWS = MAX_P16_ROWS   # the 31-bit byte offsets of the P16 retrieval kernels: rows * 1024 < 2^31 (2**21 - 1)
 SMALL_Q = 32              # the panel width of trid_index_search_p16
 MAX_K = 16
 
@@ -355,12 +357,8 @@ class GalleryIndex:
         if Q <= SMALL_Q:
             self._search_small(x, k, normalize, vals, rows)
             return vals, rows
-        from . import evaluation as E
-
         q = ops.l2norm_rows(x)[0] if normalize else x
-        ws = ops.empty((ops.L.load().trid_topk_ws_floats(Q, G, k),), q)
-        E._sim_topk_call(q, self._rows[:G], vals, rows, k, 0, ws, g16=self._p16[:G], ga=self._unit)
-        return vals, rows
+        return _Operands(q, self._rows[:G], ga=self._unit, g16=self._p16[:G]).topk(k, out=(vals, rows))
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
