@@ -1,7 +1,6 @@
 // Attention-pool token kernels (m_resnet.py:103-135), row softmax, column sums,
-// and the text-encoder kernels (gru.py:48-82): embedding-table gather, masked
-// BiGRU cell forward/backward with the max-over-time fused in.
-// The dense parts (projections, recurrent h @ W_hh^T) run on trid_gemm_f32.
+// and the text encoder's embedding-table gather and its gradient (gru.py:55-60).
+// The BiGRU itself (step, cell and max-init kernels) is gru_step.hip.
 
 #include "split_common.h"
 
@@ -199,89 +198,6 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const float* __restr
     }
 }
 
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-__global__ void gru_max_init_kernel(float* __restrict__ maxv, int32_t* __restrict__ argt,
-                                    const int64_t* __restrict__ lengths, int Lmax, const int64_t* __restrict__ lmax_dev,
-                                    int B, int Hd) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * 2 * Hd) return;
-    const int b = i / (2 * Hd);
-    // pad_packed_sequence pads to the BATCH maximum (gru.py:78-79): that maximum is the host's Lmax, or - when the
-    // host only knows an upper bound (a recorded step replayed on other captions) - the device scalar
-    const long long batch_max = lmax_dev != nullptr ? lmax_dev[0] : (long long)Lmax;
-    maxv[i] = lengths[b] < batch_max ? 0.f : -INFINITY;
-    argt[i] = -1;
-}
-
-__global__ void gru_cell_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, float* __restrict__ h,
-                                    const int64_t* __restrict__ lengths, float* __restrict__ gates,
-                                    float* __restrict__ hprev, float* __restrict__ maxv, int32_t* __restrict__ argt,
-                                    int s, int Lmax, int L, int B, int Hd, long long gates_ds, long long hprev_ds) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 2 * B * Hd) return;
-    const int j = i % Hd;
-    const int b = (i / Hd) % B;
-    const int d = i / (Hd * B);
-    const int t = d == 0 ? s : Lmax - 1 - s;
-    const bool active = (long long)t < lengths[b];
-    const float hp = h[i];
-    if (hprev != nullptr) hprev[(long long)d * hprev_ds + (long long)b * Hd + j] = hp;
-    if (!active) return;
-    const float* gir = gi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
-    const float* ghr = gh + ((long long)d * B + b) * (3 * Hd);
-    const float r = sigmoidf_(gir[j] + ghr[j]);
-    const float z = sigmoidf_(gir[Hd + j] + ghr[Hd + j]);
-    const float hn_lin = ghr[2 * Hd + j];
-    const float n = tanhf(fmaf(r, hn_lin, gir[2 * Hd + j]));
-    const float hnew = (1.f - z) * n + z * hp;
-    h[i] = hnew;
-    if (gates != nullptr) {
-        float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
-        gs[j] = r; gs[Hd + j] = z; gs[2 * Hd + j] = n; gs[3 * Hd + j] = hn_lin;
-    }
-    const int mc = b * 2 * Hd + d * Hd + j;
-    // first-index-wins on ties, like torch.max(dim): forward walks t upward, reverse downward
-    const float cur = maxv[mc];
-    if (d == 0 ? (hnew > cur) : (hnew >= cur)) {
-        maxv[mc] = hnew;
-        argt[mc] = t;
-    }
-}
-
-__global__ void gru_cell_bwd_kernel(const float* __restrict__ dout, const int32_t* __restrict__ argt,
-                                    const float* __restrict__ gates, const float* __restrict__ hprev,
-                                    const int64_t* __restrict__ lengths, float* __restrict__ dh,
-                                    float* __restrict__ dGi, float* __restrict__ dgh, int s, int Lmax, int L, int B,
-                                    int Hd, long long gates_ds, long long hprev_ds, long long dgh_ds) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 2 * B * Hd) return;
-    const int j = i % Hd;
-    const int b = (i / Hd) % B;
-    const int d = i / (Hd * B);
-    const int t = d == 0 ? s : Lmax - 1 - s;
-    const bool active = (long long)t < lengths[b];
-    float* dgir = dGi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
-    float* dghr = dgh + (long long)d * dgh_ds + (long long)b * (3 * Hd);
-    if (!active) {
-        dgir[j] = 0.f; dgir[Hd + j] = 0.f; dgir[2 * Hd + j] = 0.f;
-        dghr[j] = 0.f; dghr[Hd + j] = 0.f; dghr[2 * Hd + j] = 0.f;
-        return;
-    }
-    float dhv = dh[i];
-    const int mc = b * 2 * Hd + d * Hd + j;
-    if (argt[mc] == t) dhv += dout[mc];
-    const float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
-    const float r = gs[j], z = gs[Hd + j], n = gs[2 * Hd + j], hn_lin = gs[3 * Hd + j];
-    const float hp = hprev[(long long)d * hprev_ds + (long long)b * Hd + j];
-    const float dn_pre = dhv * (1.f - z) * (1.f - n * n);
-    const float dz_pre = dhv * (hp - n) * z * (1.f - z);
-    const float dr_pre = dn_pre * hn_lin * r * (1.f - r);
-    dgir[j] = dr_pre; dgir[Hd + j] = dz_pre; dgir[2 * Hd + j] = dn_pre;
-    dghr[j] = dr_pre; dghr[Hd + j] = dz_pre; dghr[2 * Hd + j] = dn_pre * r;
-    dh[i] = dhv * z;
-}
-
 }  // namespace trid
 
 using namespace trid;
@@ -361,36 +277,4 @@ extern "C" int trid_embedding_bwd_f32(const float* dX, const int64_t* tokens, in
     hipLaunchKernelGGL(embedding_bwd_kernel, dim3(B * L), dim3(256), 0, (hipStream_t)stream, dX, tokens, ldtok, L, B * L, E, dtable,
                        vocab, padding_idx);
     return check_launch("trid_embedding_bwd_f32");
-}
-
-extern "C" int trid_gru_max_init_f32(float* maxv, int32_t* argt, const int64_t* lengths, int Lmax, const int64_t* lmax_dev,
-                                     int B, int Hd, void* stream) {
-    TRID_REQUIRE(maxv && argt && lengths && B > 0 && Hd > 0 && Lmax > 0, "trid_gru_max_init_f32: bad arguments");
-    const int n = B * 2 * Hd;
-    hipLaunchKernelGGL(gru_max_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, maxv, argt, lengths,
-                       Lmax, lmax_dev, B, Hd);
-    return check_launch("trid_gru_max_init_f32");
-}
-
-extern "C" int trid_gru_cell_fwd_f32(const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
-                                     float* hprev, float* maxv, int32_t* argt, int s, int Lmax, int L, int B, int Hd,
-                                     long long gates_dstride, long long hprev_dstride, void* stream) {
-    TRID_REQUIRE(gi && gh && h && lengths && maxv && argt, "trid_gru_cell_fwd_f32: null pointer");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_fwd_f32: bad step/shape");
-    const int n = 2 * B * Hd;
-    hipLaunchKernelGGL(gru_cell_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, gi, gh, h, lengths,
-                       gates, hprev, maxv, argt, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride);
-    return check_launch("trid_gru_cell_fwd_f32");
-}
-
-extern "C" int trid_gru_cell_bwd_f32(const float* dout, const int32_t* argt, const float* gates, const float* hprev,
-                                     const int64_t* lengths, float* dh, float* dGi, float* dgh, int s, int Lmax, int L,
-                                     int B, int Hd, long long gates_dstride, long long hprev_dstride,
-                                     long long dgh_dstride, void* stream) {
-    TRID_REQUIRE(dout && argt && gates && hprev && lengths && dh && dGi && dgh, "trid_gru_cell_bwd_f32: null pointer");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_bwd_f32: bad step/shape");
-    const int n = 2 * B * Hd;
-    hipLaunchKernelGGL(gru_cell_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, argt, gates,
-                       hprev, lengths, dh, dGi, dgh, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride, dgh_dstride);
-    return check_launch("trid_gru_cell_bwd_f32");
 }

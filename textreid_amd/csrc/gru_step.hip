@@ -393,32 +393,51 @@ __global__ __launch_bounds__(GTHREADS) void gru_step_bwd_kernel(GruBwdParams p) 
     }
 }
 
-// ---- The unfused pair of a step (one batched GEMM h @ W_hh^T + one cell kernel: H outside 32..768, TRID_FUSED_GRU=0) in
-// the sequence form: as gru_cell_fwd_kernel / gru_cell_bwd_kernel (attn_text.hip), yseq / dyseq in place of the max.
-__device__ __forceinline__ float sigmoid_exact_(float v) { return 1.f / (1.f + expf(-v)); }
+// ---- The unfused pair of a step (one batched GEMM h @ W_hh^T + one cell kernel: H outside 32..768, TRID_FUSED_GRU=0), in
+// the two output forms of the step kernels above: the running max (maxv, argt; the max init sets up the zero-pad behaviour of
+// gru.py:63) or, SEQ, yseq / dyseq in place of the max.
+__device__ __forceinline__ float sigmoid_expf_(float v) { return 1.f / (1.f + expf(-v)); }  // (libm's expf, not sigmoid_'s __expf)
 
-__global__ void gru_cell_seq_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, float* __restrict__ h,
-                                        const int64_t* __restrict__ lengths, float* __restrict__ gates,
-                                        float* __restrict__ hprev, float* __restrict__ yseq, int s, int Lmax, int L, int B,
-                                        int Hd, long long gates_ds, long long hprev_ds) {
+__global__ void gru_max_init_kernel(float* __restrict__ maxv, int32_t* __restrict__ argt,
+                                    const int64_t* __restrict__ lengths, int Lmax, const int64_t* __restrict__ lmax_dev,
+                                    int B, int Hd) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2LL * B * Hd) return;
-    const int j = (int)(i % Hd);
-    const int b = (int)((i / Hd) % B);
-    const int d = (int)(i / ((long long)Hd * B));
+    const int b = (int)(i / (2 * Hd));
+    // pad_packed_sequence pads to the BATCH maximum (gru.py:78-79): that maximum is the host's Lmax, or - when the
+    // host only knows an upper bound (a recorded step replayed on other captions) - the device scalar
+    const long long batch_max = lmax_dev != nullptr ? lmax_dev[0] : (long long)Lmax;
+    maxv[i] = lengths[b] < batch_max ? 0.f : -INFINITY;
+    argt[i] = -1;
+}
+
+template <bool SEQ>
+__global__ void gru_cell_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, float* __restrict__ h,
+                                    const int64_t* __restrict__ lengths, float* __restrict__ gates,
+                                    float* __restrict__ hprev, float* __restrict__ maxv, int32_t* __restrict__ argt,
+                                    float* __restrict__ yseq, int s, int Lmax, int L, int B, int Hd, long long gates_ds,
+                                    long long hprev_ds) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2LL * B * Hd) return;
+    const int row = (int)(i / Hd);  // d * B + b < 2B: the one 64-bit division of the index
+    const int j = (int)(i - (long long)row * Hd);
+    const int d = row >= B ? 1 : 0;
+    const int b = row - d * B;
     const int t = d == 0 ? s : Lmax - 1 - s;
     const bool active = (long long)t < lengths[b];
     const float hp = h[i];
     if (hprev != nullptr) hprev[(long long)d * hprev_ds + (long long)b * Hd + j] = hp;
-    float* yr = yseq + ((long long)b * L + t) * (2 * Hd) + (long long)d * Hd;
+    float* yr = SEQ ? yseq + ((long long)b * L + t) * (2 * Hd) + (long long)d * Hd : nullptr;  // this step's yseq row
+    // (a row pointer formed up here, not an element index: with the index the compiler pairs the two products of hnew into a
+    // packed multiply + add instead of multiply + fma, and tests/test_gru_flow_gpu.py holds the bits)
     if (!active) {
-        yr[j] = 0.f;
+        if constexpr (SEQ) yr[j] = 0.f;
         return;
     }
     const float* gir = gi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
     const float* ghr = gh + ((long long)d * B + b) * (3 * Hd);
-    const float r = sigmoid_exact_(gir[j] + ghr[j]);
-    const float z = sigmoid_exact_(gir[Hd + j] + ghr[Hd + j]);
+    const float r = sigmoid_expf_(gir[j] + ghr[j]);
+    const float z = sigmoid_expf_(gir[Hd + j] + ghr[Hd + j]);
     const float hn_lin = ghr[2 * Hd + j];
     const float n = tanhf(fmaf(r, hn_lin, gir[2 * Hd + j]));
     const float hnew = (1.f - z) * n + z * hp;
@@ -427,19 +446,32 @@ __global__ void gru_cell_seq_fwd_kernel(const float* __restrict__ gi, const floa
         float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
         gs[j] = r; gs[Hd + j] = z; gs[2 * Hd + j] = n; gs[3 * Hd + j] = hn_lin;
     }
-    yr[j] = hnew;
+    if constexpr (SEQ) {
+        yr[j] = hnew;
+    } else {
+        const long long mc = (long long)b * 2 * Hd + (long long)d * Hd + j;
+        // first-index-wins on ties, like torch.max(dim): forward walks t upward, reverse downward
+        const float cur = maxv[mc];
+        if (d == 0 ? (hnew > cur) : (hnew >= cur)) {
+            maxv[mc] = hnew;
+            argt[mc] = t;
+        }
+    }
 }
 
-__global__ void gru_cell_seq_bwd_kernel(const float* __restrict__ dyseq, const float* __restrict__ gates,
-                                        const float* __restrict__ hprev, const int64_t* __restrict__ lengths,
-                                        float* __restrict__ dh, float* __restrict__ dGi, float* __restrict__ dgh, int s,
-                                        int Lmax, int L, int B, int Hd, long long gates_ds, long long hprev_ds,
-                                        long long dgh_ds) {
+template <bool SEQ>
+__global__ void gru_cell_bwd_kernel(const float* __restrict__ dout, const int32_t* __restrict__ argt,
+                                    const float* __restrict__ dyseq, const float* __restrict__ gates,
+                                    const float* __restrict__ hprev, const int64_t* __restrict__ lengths,
+                                    float* __restrict__ dh, float* __restrict__ dGi, float* __restrict__ dgh, int s,
+                                    int Lmax, int L, int B, int Hd, long long gates_ds, long long hprev_ds,
+                                    long long dgh_ds) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2LL * B * Hd) return;
-    const int j = (int)(i % Hd);
-    const int b = (int)((i / Hd) % B);
-    const int d = (int)(i / ((long long)Hd * B));
+    const int row = (int)(i / Hd);  // d * B + b < 2B: the one 64-bit division of the index
+    const int j = (int)(i - (long long)row * Hd);
+    const int d = row >= B ? 1 : 0;
+    const int b = row - d * B;
     const int t = d == 0 ? s : Lmax - 1 - s;
     const bool active = (long long)t < lengths[b];
     float* dgir = dGi + ((long long)b * L + t) * (6 * Hd) + (long long)d * 3 * Hd;
@@ -449,7 +481,13 @@ __global__ void gru_cell_seq_bwd_kernel(const float* __restrict__ dyseq, const f
         dghr[j] = 0.f; dghr[Hd + j] = 0.f; dghr[2 * Hd + j] = 0.f;
         return;
     }
-    const float dhv = dh[i] + dyseq[((long long)b * L + t) * (2 * Hd) + (long long)d * Hd + j];
+    float dhv = dh[i];
+    if constexpr (SEQ) {
+        dhv += dyseq[((long long)b * L + t) * (2 * Hd) + (long long)d * Hd + j];
+    } else {
+        const long long mc = (long long)b * 2 * Hd + (long long)d * Hd + j;
+        if (argt[mc] == t) dhv += dout[mc];
+    }
     const float* gs = gates + (long long)d * gates_ds + (long long)b * (4 * Hd);
     const float r = gs[j], z = gs[Hd + j], n = gs[2 * Hd + j], hn_lin = gs[3 * Hd + j];
     const float hp = hprev[(long long)d * hprev_ds + (long long)b * Hd + j];
@@ -589,24 +627,65 @@ extern "C" int trid_gru_step_seq_bwd_f32(const void* img_bwd, const float* w_ama
                                  hprev, lengths, dh, dGi, dgh_out, s, Lmax, L, B, H, gates_dstride, hprev_dstride, dgh_dstride, stream);
 }
 
+extern "C" int trid_gru_max_init_f32(float* maxv, int32_t* argt, const int64_t* lengths, int Lmax, const int64_t* lmax_dev,
+                                     int B, int Hd, void* stream) {
+    TRID_REQUIRE(maxv && argt && lengths && B > 0 && Hd > 0 && Lmax > 0, "trid_gru_max_init_f32: bad arguments");
+    const long long n = 2LL * B * Hd;
+    hipLaunchKernelGGL(gru_max_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, maxv, argt, lengths,
+                       Lmax, lmax_dev, B, Hd);
+    return check_launch("trid_gru_max_init_f32");
+}
+
+// the two forms of an unfused cell update, as launch_step_fwd / launch_step_bwd above
+template <bool SEQ>
+static int launch_cell_fwd(const char* what, const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
+                           float* hprev, float* maxv, int32_t* argt, float* yseq, int s, int Lmax, int L, int B, int Hd,
+                           long long gates_dstride, long long hprev_dstride, void* stream) {
+    TRID_REQUIRE(gi && gh && h && lengths && (SEQ ? yseq != nullptr : (maxv && argt)), "%s: null pointer", what);
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "%s: bad step/shape", what);
+    const long long n = 2LL * B * Hd;
+    hipLaunchKernelGGL(gru_cell_fwd_kernel<SEQ>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi, gh, h, lengths,
+                       gates, hprev, maxv, argt, yseq, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride);
+    return check_launch(what);
+}
+
+extern "C" int trid_gru_cell_fwd_f32(const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
+                                     float* hprev, float* maxv, int32_t* argt, int s, int Lmax, int L, int B, int Hd,
+                                     long long gates_dstride, long long hprev_dstride, void* stream) {
+    return launch_cell_fwd<false>("trid_gru_cell_fwd_f32", gi, gh, h, lengths, gates, hprev, maxv, argt, nullptr, s, Lmax, L, B, Hd,
+                                  gates_dstride, hprev_dstride, stream);
+}
+
 extern "C" int trid_gru_cell_seq_fwd_f32(const float* gi, const float* gh, float* h, const int64_t* lengths, float* gates,
                                          float* hprev, float* yseq, int s, int Lmax, int L, int B, int Hd,
                                          long long gates_dstride, long long hprev_dstride, void* stream) {
-    TRID_REQUIRE(gi && gh && h && lengths && yseq, "trid_gru_cell_seq_fwd_f32: null pointer");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_seq_fwd_f32: bad step/shape");
+    return launch_cell_fwd<true>("trid_gru_cell_seq_fwd_f32", gi, gh, h, lengths, gates, hprev, nullptr, nullptr, yseq, s, Lmax, L, B, Hd,
+                                 gates_dstride, hprev_dstride, stream);
+}
+
+template <bool SEQ>
+static int launch_cell_bwd(const char* what, const float* dout, const int32_t* argt, const float* dyseq, const float* gates,
+                           const float* hprev, const int64_t* lengths, float* dh, float* dGi, float* dgh, int s, int Lmax, int L,
+                           int B, int Hd, long long gates_dstride, long long hprev_dstride, long long dgh_dstride, void* stream) {
+    TRID_REQUIRE((SEQ ? dyseq != nullptr : (dout && argt)) && gates && hprev && lengths && dh && dGi && dgh, "%s: null pointer", what);
+    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "%s: bad step/shape", what);
     const long long n = 2LL * B * Hd;
-    hipLaunchKernelGGL(gru_cell_seq_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi, gh, h, lengths,
-                       gates, hprev, yseq, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride);
-    return check_launch("trid_gru_cell_seq_fwd_f32");
+    hipLaunchKernelGGL(gru_cell_bwd_kernel<SEQ>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dout, argt, dyseq,
+                       gates, hprev, lengths, dh, dGi, dgh, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride, dgh_dstride);
+    return check_launch(what);
+}
+
+extern "C" int trid_gru_cell_bwd_f32(const float* dout, const int32_t* argt, const float* gates, const float* hprev,
+                                     const int64_t* lengths, float* dh, float* dGi, float* dgh, int s, int Lmax, int L,
+                                     int B, int Hd, long long gates_dstride, long long hprev_dstride,
+                                     long long dgh_dstride, void* stream) {
+    return launch_cell_bwd<false>("trid_gru_cell_bwd_f32", dout, argt, nullptr, gates, hprev, lengths, dh, dGi, dgh, s, Lmax, L, B, Hd,
+                                  gates_dstride, hprev_dstride, dgh_dstride, stream);
 }
 
 extern "C" int trid_gru_cell_seq_bwd_f32(const float* dyseq, const float* gates, const float* hprev, const int64_t* lengths,
                                          float* dh, float* dGi, float* dgh, int s, int Lmax, int L, int B, int Hd,
                                          long long gates_dstride, long long hprev_dstride, long long dgh_dstride, void* stream) {
-    TRID_REQUIRE(dyseq && gates && hprev && lengths && dh && dGi && dgh, "trid_gru_cell_seq_bwd_f32: null pointer");
-    TRID_REQUIRE(s >= 0 && s < Lmax && Lmax <= L && B > 0 && Hd > 0, "trid_gru_cell_seq_bwd_f32: bad step/shape");
-    const long long n = 2LL * B * Hd;
-    hipLaunchKernelGGL(gru_cell_seq_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dyseq, gates, hprev,
-                       lengths, dh, dGi, dgh, s, Lmax, L, B, Hd, gates_dstride, hprev_dstride, dgh_dstride);
-    return check_launch("trid_gru_cell_seq_bwd_f32");
+    return launch_cell_bwd<true>("trid_gru_cell_seq_bwd_f32", nullptr, nullptr, dyseq, gates, hprev, lengths, dh, dGi, dgh, s, Lmax, L, B,
+                                 Hd, gates_dstride, hprev_dstride, dgh_dstride, stream);
 }
