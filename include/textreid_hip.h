@@ -785,6 +785,16 @@ int trid_index_search_masked_p16(const void* q16, const void* g16, const float* 
  * 0 for rows >= n.  live / allow: uint8 [n] on the device; either may be NULL (it then counts as all ones), not both.
  * n_words >= ceil(n / 32); EVERY word up to n_words is written.  No host read, no allocation. */
 int trid_index_pack_mask_u32(const uint8_t* live, const uint8_t* allow, int n, uint32_t* words, int n_words, void* stream);
+/* The same search over distinct GROUPS (GalleryIndex.search_pids: the k best people, not the k best images): group_ids = int32 [G]
+ * on the device, 4-byte aligned, equal ids = one group (only equality matters; any int32).  The representative of a group for a
+ * query is its first allowed row in the order above; the result is the first k representatives in that order - at most one row per
+ * group, exact, in the same single pass: every list of the kernel holds at most one entry per group.  mask_words as in the masked
+ * search, or NULL: every row allowed.  With all ids different the result equals trid_index_search_masked_p16 bit for bit.  A query
+ * with fewer than k allowed groups gets its real results first, then (-inf, -1) slots.  Arithmetic, order, limits and ws
+ * (trid_index_search_ws_bytes) as trid_index_search_p16; group_ids is read by both launches. */
+int trid_index_search_distinct_p16(const void* q16, const void* g16, const float* unit_amax, const int32_t* group_ids,
+                                   const uint32_t* mask_words, int Q, int G, int k, long long idx_offset, float* out_val,
+                                   int64_t* out_idx, void* ws, int workgroups, void* stream);
 
 /* per-row top-k of a given similarity matrix (rank(get_mAP=False), evaluation.py:17-19) */
 int trid_topk_rows_f32(const float* sim, int ld, int Q, int G, int k, float* out_val, int64_t* out_idx,

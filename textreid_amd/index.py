@@ -31,11 +31,21 @@ never tightens the threshold, so the answer is the exact top-k of the allowed ro
     -> new-row map; afterwards there are no tombstones and searches run the unmasked path again.
 An index that never saw ``remove`` and is searched without ``mask`` runs exactly the unmasked path (``trid_index_search_p16``).
 
+``search_pids`` answers "which k PEOPLE are best" where ``search`` answers "which k rows": a gallery holds several images per person
+and in a list of rows a person with many good images crowds every other identity out.  The representative of a pid for a query is
+its first allowed row in the order above; the result is the first k representatives in that order - at most one row per pid, ties
+to the lower row inside a pid and between pids.  It is exact and still ONE pass (``trid_index_search_distinct_p16``, DESIGN.md section
+7g): every list of the kernel holds at most one entry per person.  The kernel compares int32 group ids (``group_ids(pids)``: equal
+pids = equal ids), derived state like the mask words: a cached buffer, rebuilt by the first ``search_pids`` after ``add`` /
+``compact`` / ``load_state_dict`` / growth (``remove`` leaves it valid).  The allow set composes as in ``search``: a removed or
+masked row is never a representative, a pid without allowed rows is absent.  The number of distinct pids is never read back: a
+query with fewer than k of them ends in ``(-inf, -1, -1)`` slots.  More than 32 queries run in panels of 32.
+
 An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
 A recorded search answers against the gallery as it stood at the capture (row count, storage and tombstones are part of the
 recording): record again after ``add`` / ``remove`` / ``compact``.
 
-Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, top-k over distinct pids, an
+Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output).
 """
 
@@ -56,6 +66,21 @@ def _need_cuda(name, t):
         raise RuntimeError("textreid_amd.index.GalleryIndex.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
 
 
+def group_ids(pids):
+    """int32 [n] on the device of ``pids``: equal pids <=> equal ids (the rank of the pid among the distinct pids, so < n whatever
+    the int64 values are).  No host read: stable sort, boundaries, running count, scattered back through the permutation."""
+    p = torch.as_tensor(pids).reshape(-1).long()
+    n = p.numel()
+    out = torch.empty(n, dtype=torch.int32, device=p.device)
+    if n == 0:
+        return out
+    ordered, perm = torch.sort(p, stable=True)
+    step = torch.zeros(n, dtype=torch.int32, device=p.device)
+    step[1:] = ordered[1:] != ordered[:-1]
+    out[perm] = torch.cumsum(step, 0, dtype=torch.int32)
+    return out
+
+
 class GalleryIndex:
     """``idx = GalleryIndex(); idx.add(image_embed, pids); vals, rows = idx.search(text_embed, k=10)``.  See the module docstring
     for the storage, the order rule, the one-stream rule and what is out of scope."""
@@ -74,6 +99,7 @@ class GalleryIndex:
         self._live = None   # bool [capacity]: False = removed (the single source of truth for tombstones)
         self._dead = 0      # removed rows among the first len (host count)
         self._words_ok = False  # the cached mask words of the tombstones are current
+        self._gids_ok = False   # the cached group ids of the pids are current
         self._has_pids = None
         self._unit = None   # device scalar 1.0: the amax every row and every query is packed with
         self._ws = {}       # the cached workspace of the small-batch search
@@ -136,7 +162,7 @@ class GalleryIndex:
             pids[: self._n].copy_(self._pids[: self._n])
             live[: self._n].copy_(self._live[: self._n])
         self._rows, self._p16, self._pids, self._live = rows, p16, pids, live
-        self._words_ok = False
+        self._words_ok = self._gids_ok = False
         if self._unit is None:
             self._unit = torch.ones(1, dtype=torch.float32, device=device)
 
@@ -186,7 +212,7 @@ class GalleryIndex:
         self._has_pids = has
         self._live[first : first + n] = True
         self._n = first + n
-        self._words_ok = False
+        self._words_ok = self._gids_ok = False
         return first
 
     # ------------------------------------------------------------------ removal
@@ -244,7 +270,7 @@ class GalleryIndex:
         pids[:m] = self._pids[keep]
         self._rows, self._p16, self._pids = rows, p16, pids
         self._live = torch.ones(cap, dtype=torch.bool, device=dev)
-        self._n, self._dead, self._words_ok = m, 0, False
+        self._n, self._dead, self._words_ok, self._gids_ok = m, 0, False, False
         if m == 0:
             self._has_pids = None
         return new_of
@@ -293,9 +319,23 @@ class GalleryIndex:
         call("trid_index_pack_mask_u32", _p(self._live) if self._dead else None, _p(mask), n, _p(words), words.numel(), stream())
         return words
 
-    def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None):
+    def _group_ids(self):
+        """-> the cached int32 group ids of the pids, one per row of the CAPACITY (the first len are meaningful): rebuilt after add /
+        compact / load_state_dict / growth, outside any capture like the workspace.  remove leaves them valid."""
+        buf = self._ws.get("gids")
+        if buf is None or buf.numel() < self.capacity:
+            buf = torch.zeros(self.capacity, dtype=torch.int32, device=self._rows.device)
+            self._ws["gids"] = buf
+            self._gids_ok = False
+        if not self._gids_ok:
+            buf[: self._n].copy_(group_ids(self._pids[: self._n]))
+            self._gids_ok = True
+        return buf
+
+    def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None, gids=None):
         """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read.
-        words: the packed allow bits (the masked kernel); None: every row may be returned."""
+        words: the packed allow bits (the masked kernel); None: every row may be returned.  gids: the rows' group ids (the
+        distinct kernel: at most one row per group)."""
         Q, G = x.shape[0], self._n
         L = ops.L.load()
         need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
@@ -307,10 +347,41 @@ class GalleryIndex:
             q16[Q : self._panel_rows].zero_()
         self._panel_rows = Q
         call("trid_p16_pack_f32", _p(x), Q, self.dim, self.dim, _p(self._unit), _p(q16), 1, stream())
-        if words is None:
+        if gids is not None:
+            call("trid_index_search_distinct_p16", _p(q16), _p(self._p16), _p(self._unit), _p(gids), None if words is None else _p(words), Q, G, k, 0,
+                 _p(vals), _p(rows), _p(lists), workgroups, stream())
+        elif words is None:
             call("trid_index_search_p16", _p(q16), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
         else:
             call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+
+    def _check_search(self, name, queries, k, mask, need_pids=False):
+        """the argument rules search and search_pids share, in the order the messages are promised -> the queries, fp32 contiguous"""
+        if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError("GalleryIndex.%s: expected a [Q, %d] tensor" % (name, self.dim))
+        if need_pids and not self._has_pids:
+            raise ValueError("GalleryIndex.%s: the index holds no pids" % name)
+        G = self._n
+        if G == 0:
+            raise ValueError("GalleryIndex.%s: the index is empty" % name)
+        if k < 1 or k > MAX_K or k > G:
+            raise ValueError("GalleryIndex.%s: k must be in [1, %d] and <= len(index) = %d; got %d" % (name, MAX_K, G, k))
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("GalleryIndex.%s: mask must be a bool or uint8 tensor; got %s" % (name, mask.dtype if torch.is_tensor(mask) else type(mask)))
+            if mask.dim() != 1 or mask.shape[0] != G:
+                raise ValueError("GalleryIndex.%s: mask must have shape [len(index) = %d]; got %s" % (name, G, tuple(mask.shape)))
+        elif k > self.live_count:
+            raise ValueError("GalleryIndex.%s: k must be <= live_count = %d (%d of %d rows were removed); got %d" % (name, self.live_count, self._dead, G, k))
+        if queries.shape[0] == 0:
+            raise ValueError("GalleryIndex.%s: no queries" % name)
+        _need_cuda(name, queries)
+        x = queries.contiguous().float()
+        if x.device != self._rows.device:
+            raise ValueError("GalleryIndex.%s: the index lives on %s; got queries on %s" % (name, self._rows.device, x.device))
+        if mask is not None and mask.device != self._rows.device:
+            raise ValueError("GalleryIndex.%s: the index lives on %s; got a mask on %s" % (name, self._rows.device, mask.device))
+        return x
 
     def search(self, queries, k=10, normalize=True, mask=None):
         """-> (values [Q,k] f32, rows [Q,k] i64), value descending then row ascending.  Q <= 32: one pass of
@@ -321,29 +392,8 @@ class GalleryIndex:
         contents are read at replay time; the tombstones are part of the recording - record again after add / remove / compact),
         in panels of 32 queries when Q > 32 (one gallery pass per panel: compact() before bulk queries).  Removed rows only:
         k <= live_count.  With a mask: a query with fewer than k allowed rows ends in (-inf, -1) slots."""
-        if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise ValueError("GalleryIndex.search: expected a [Q, %d] tensor" % self.dim)
-        G = self._n
-        if G == 0:
-            raise ValueError("GalleryIndex.search: the index is empty")
-        if k < 1 or k > MAX_K or k > G:
-            raise ValueError("GalleryIndex.search: k must be in [1, %d] and <= len(index) = %d; got %d" % (MAX_K, G, k))
-        if mask is not None:
-            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
-                raise ValueError("GalleryIndex.search: mask must be a bool or uint8 tensor; got %s" % (mask.dtype if torch.is_tensor(mask) else type(mask)))
-            if mask.dim() != 1 or mask.shape[0] != G:
-                raise ValueError("GalleryIndex.search: mask must have shape [len(index) = %d]; got %s" % (G, tuple(mask.shape)))
-        elif k > self.live_count:
-            raise ValueError("GalleryIndex.search: k must be <= live_count = %d (%d of %d rows were removed); got %d" % (self.live_count, self._dead, G, k))
-        Q = queries.shape[0]
-        if Q == 0:
-            raise ValueError("GalleryIndex.search: no queries")
-        _need_cuda("search", queries)
-        x = queries.contiguous().float()
-        if x.device != self._rows.device:
-            raise ValueError("GalleryIndex.search: the index lives on %s; got queries on %s" % (self._rows.device, x.device))
-        if mask is not None and mask.device != self._rows.device:
-            raise ValueError("GalleryIndex.search: the index lives on %s; got a mask on %s" % (self._rows.device, mask.device))
+        x = self._check_search("search", queries, k, mask)
+        Q, G = x.shape[0], self._n
         vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
         rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
         if mask is not None or self._dead:
@@ -360,6 +410,24 @@ class GalleryIndex:
         q = ops.l2norm_rows(x)[0] if normalize else x
         return _Operands(q, self._rows[:G], ga=self._unit, g16=self._p16[:G]).topk(k, out=(vals, rows))
 
+    def search_pids(self, queries, k=10, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64, pids [Q,k] i64): the k best DISTINCT pids of every query, each by its best allowed
+        row (value descending, then row ascending, inside a pid and between pids); pids = self.pids[rows].  One pass of
+        trid_index_search_distinct_p16 per 32 queries, no host read; capturable with torch.cuda.graph after one eager call (which
+        builds the cached group ids and workspaces): a replay reads the queries' and the mask's contents at replay time; record
+        again after add / remove / compact.  queries, k, normalize, mask: as search (no mask: k <= live_count).  The index must
+        hold pids.  A query with fewer than k distinct allowed pids ends in (-inf, -1, -1) slots."""
+        x = self._check_search("search_pids", queries, k, mask, need_pids=True)
+        Q, G = x.shape[0], self._n
+        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
+        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        gids = self._group_ids()
+        for at in range(0, Q, SMALL_Q):  # panels of 32 queries, one gallery pass each, into slices of the outputs
+            self._search_small(x[at : at + SMALL_Q], k, normalize, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], words=words, gids=gids)
+        pids = self._pids[:G][rows].masked_fill_(rows < 0, -1)  # (a short slot's -1 indexes the last row: in range, then overwritten)
+        return vals, rows, pids
+
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
         """the normalised fp32 rows, the pids (None without) and the liveness (bool [len]; None when nothing was removed); P16 is
@@ -373,7 +441,7 @@ class GalleryIndex:
         state dict without "live" (as written before removal existed) loads as all-live."""
         rows = sd["rows"]
         if rows is None or rows.shape[0] == 0:
-            self._n, self._has_pids, self._dead, self._words_ok = 0, None, 0, False
+            self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
             return
         if rows.shape[0] > MAX_ROWS:
             raise ValueError("GalleryIndex.load_state_dict: at most %d rows; got %d" % (MAX_ROWS, rows.shape[0]))
@@ -382,7 +450,7 @@ class GalleryIndex:
         live = sd.get("live")
         if live is not None and (not torch.is_tensor(live) or live.numel() != n):
             raise ValueError("GalleryIndex.load_state_dict: live must hold one entry per row (%d)" % n)
-        self._n, self._has_pids, self._dead, self._words_ok = 0, None, 0, False
+        self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
         self._reserve(n, x.device)
         self._rows[:n].copy_(x)
         self._pack_into(0, n)

@@ -7,7 +7,7 @@ Under torch.distributed.run with more than one rank --map times the SHARDED form
 positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
-usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]]
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -15,7 +15,10 @@ median and the spread (min, max) of each in ms, the bytes the index search needs
 add time.  --wg N forces the number of workers of the one-pass kernel (tuning).
 --masked [F]: a fourth form, index_masked, timed in the same process alternating with the others: the same search on a second index
 over the same gallery from which the fraction F (default 0.1) of the rows was removed (the masked one-pass kernel; panels of 32 queries
-for Q > 32).  Each Q entry gains index_masked_ms and masked_over_index = its median over the unmasked index search's median."""
+for Q > 32).  Each Q entry gains index_masked_ms and masked_over_index = its median over the unmasked index search's median.
+--distinct [M]: a further form, index_distinct, timed in the same process alternating with the others: GalleryIndex.search_pids on an
+index over the same gallery with M rows per pid (default 4; pid = a fixed random permutation of the rows // M: the distinct one-pass
+kernel, panels of 32 queries for Q > 32).  Each Q entry gains index_distinct_ms and distinct_over_index."""
 import json, os, sys, time
 import torch
 
@@ -30,6 +33,12 @@ def index_main(argv):
         i = argv.index("--wg")
         wg = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    distinct = None
+    if "--distinct" in argv:  # (--distinct M comes last or before another option: a bare number after it is M)
+        i = argv.index("--distinct")
+        given = i + 1 < len(argv) and not argv[i + 1].startswith("--")
+        distinct = int(argv[i + 1]) if given else 4
+        argv = argv[:i] + argv[i + (2 if given else 1):]
     masked = None
     if "--masked" in argv:
         i = argv.index("--masked")
@@ -56,6 +65,12 @@ def index_main(argv):
         gone = torch.nonzero(torch.rand(G, generator=gen) < masked).reshape(-1)
         line["masked_fraction"], line["masked_removed"] = masked, idx_m.remove(rows=gone)
         torch.cuda.synchronize()
+    idx_d = None
+    if distinct is not None:
+        idx_d = GalleryIndex(capacity=G)
+        idx_d.add(g_raw, pids=torch.randperm(G, generator=gen) // distinct)
+        line["distinct_rows_per_pid"] = distinct
+        torch.cuda.synchronize()
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -74,6 +89,8 @@ def index_main(argv):
                  "topk_unit": lambda: E.similarity_topk(q_unit, g_unit, K, normalize=False)}
         if idx_m is not None:
             forms["index_masked"] = (lambda: idx_m.search(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx_m._search_small(q_raw, K, True, out_v, out_r, wg, idx_m._mask_words(None)))
+        if idx_d is not None:
+            forms["index_distinct"] = (lambda: idx_d.search_pids(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx_d._search_small(q_raw, K, True, out_v, out_r, wg, None, idx_d._group_ids()))
         for fn in forms.values():
             for _ in range(WARM):
                 fn()
@@ -96,6 +113,8 @@ def index_main(argv):
         if idx_m is not None:
             ent["masked_over_index"] = ent["index_masked_ms"]["median"] / ent["index_ms"]["median"]
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
+        if idx_d is not None:
+            ent["distinct_over_index"] = ent["index_distinct_ms"]["median"] / ent["index_ms"]["median"]
         a, b = idx.search(q_raw, K), E.similarity_topk(q_raw, g_raw, K)
         ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
         ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
