@@ -799,6 +799,25 @@ int trid_index_search_distinct_p16(const void* q16, const void* g16, const float
 /* per-row top-k of a given similarity matrix (rank(get_mAP=False), evaluation.py:17-19) */
 int trid_topk_rows_f32(const float* sim, int ld, int Q, int G, int k, float* out_val, int64_t* out_idx,
                        void* stream);
+/* DEEP per-row top-k of a given score matrix (csrc/topk_deep.hip; evaluation.rank(get_mAP=False) beyond 16, evaluation.topk_rows,
+ * GalleryIndex.shortlist): exact for 1 <= k <= 1024 (k <= G as in the other entries), Q >= 1 with no limit but the grid: one launch
+ * of Q * ceil(G / chunk) workgroups of 256 threads, and the runtime takes fewer than 2^32 threads, so the product must be < 2^24.  Element (q, g) = sim[q * ld_q + g * ld_g]: row-major [Q, G] (ld_q >= G, ld_g = 1) and the [G, cols]
+ * product trid_gemm_p16 writes with the gallery as A (ld_q = 1, ld_g = cols >= Q) both work; strides that make two elements alias
+ * are refused.  Order - the library's one order: value descending by float comparison, then column ascending; +0 and -0 compare
+ * equal and tie by column (the original bits are returned: the select moves values and never computes one); a real -inf is an
+ * ordinary value that sorts last and ties by column; NaN undefined (as trid_topk_rows_f32 and trid_argsort_rows_desc_f32).
+ * mask_words: the words of trid_index_pack_mask_u32, bit (g & 31) of word (g >> 5) set = column g may be returned, bits of columns
+ * >= G ignored, NULL = every column allowed.  A disallowed column is ABSENT, not -inf: a row with fewer than k allowed columns gets
+ * its real results first, then (-inf, -1) slots (-1 whatever idx_offset).  out_val [Q, k] f32, out_idx [Q, k] i64 = column +
+ * idx_offset.  No host read, no allocation, nothing but launches on `stream` whose sequence depends on (G, k, chunk) only: it can
+ * be captured - after ONE eager call on the device with any arguments, which raises the dynamic-LDS limit of every instantiation.  chunk = columns per first-level workgroup: 0 = the library's choice (trid_topk_rows_deep_chunk(k): 8192 for
+ * k <= 512, else 2048), otherwise a power of two in [max(64, 2 * next_pow2(k)), 8192] (tests, tuning).  Level 1: one workgroup per
+ * (query, chunk) orders its pairs in LDS and leaves k in ws; merge levels load chunk / k lists each until one is left.  ws: 8-byte
+ * aligned, ws_bytes >= trid_topk_rows_deep_ws_bytes with the same arguments (0 for arguments out of range; positive otherwise). */
+int trid_topk_rows_deep_chunk(int k);
+long long trid_topk_rows_deep_ws_bytes(int Q, int G, int k, int chunk);
+int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, int Q, int G, int k, const uint32_t* mask_words,
+                            long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk, void* stream);
 /* per-row full descending argsort (rank(get_mAP=True), evaluation.py:14), ties -> lower column first.  G <= 16384:
  * one in-LDS bitonic sort per row, no workspace (ws may be NULL).  Larger rows: packed keys + rocPRIM segmented radix
  * sort in the caller's workspace of trid_argsort_ws_bytes(Q, G) bytes (256-byte aligned; 0 = none needed, or Q*G >= 2^31:

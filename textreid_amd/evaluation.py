@@ -38,7 +38,59 @@ def similarity(text_embed, image_embed):
     return ops.linear(l2_normalize_rows(text_embed), l2_normalize_rows(image_embed))
 
 
+MAX_TOPK = 16        # trid_topk_rows_f32 and every one-pass top-k (csrc/topk_wave.h TOPK_MAX)
+MAX_DEEP_TOPK = 1024  # trid_topk_rows_deep_f32 (csrc/topk_deep.hip TOPK_DEEP_MAX)
+
+
+def _deep_topk(sim_ptr, ld_q, ld_g, Q, G, k, words, vals, cols, ws=None):
+    """THE launch of trid_topk_rows_deep_f32 on torch's current stream.  ws: a uint8 workspace the caller keeps between calls
+    (GalleryIndex.shortlist); None: allocated for this call, as rank does for its sort."""
+    if ws is None:
+        nws = ops.L.load().trid_topk_rows_deep_ws_bytes(Q, G, k, 0)
+        if nws <= 0:
+            raise RuntimeError("trid_topk_rows_deep_f32: Q = %d, G = %d, k = %d out of range (k must be in [1,%d] and <= G)" % (Q, G, k, MAX_DEEP_TOPK))
+        ws = torch.empty(nws, dtype=torch.uint8, device=vals.device)
+    call("trid_topk_rows_deep_f32", sim_ptr, ld_q, ld_g, Q, G, k, _p(words), 0, _p(vals), _p(cols), _p(ws), ws.numel(), 0, stream())
+
+
+def topk_rows(sim, k, mask=None):
+    """-> (values [Q,k] f32, columns [Q,k] i64): the exact k best columns of every row of a CUDA fp32 [Q, G] matrix, 1 <= k <= 1024,
+    k <= G, value descending then column ascending (trid_topk_rows_deep_f32; the values are the input's bit patterns).  The rows
+    need not be contiguous (a view such as ``sim[:, ::2]`` is read in place).  mask: bool / uint8 [G] on the same device, true = the
+    column may be returned; a row with fewer than k allowed columns ends in (-inf, -1) slots.  No host read."""
+    if not torch.is_tensor(sim) or sim.dim() != 2:
+        raise ValueError("textreid_amd.evaluation.topk_rows: expected a [Q, G] tensor")
+    if not sim.is_cuda:
+        raise RuntimeError("textreid_amd.evaluation.topk_rows runs on the HIP kernel library only (CUDA tensors); no CPU fallback")
+    Q, G = sim.shape
+    if Q < 1 or k < 1 or k > MAX_DEEP_TOPK or k > G:
+        raise ValueError("textreid_amd.evaluation.topk_rows: k must be in [1, %d] and <= G = %d, Q >= 1; got k = %d, Q = %d" % (MAX_DEEP_TOPK, G, k, Q))
+    if sim.dtype != torch.float32:
+        sim = sim.float()
+    ld_q, ld_g = (1 if Q == 1 else sim.stride(0)), (1 if G == 1 else sim.stride(1))
+    if not (ld_q >= 1 and ld_g >= 1 and (ld_q >= (G - 1) * ld_g + 1 or ld_g >= (Q - 1) * ld_q + 1)):
+        sim = sim.contiguous()  # (an expanded view: its elements alias)
+        ld_q, ld_g = G, 1
+    dev = sim.device
+    words = None
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or mask.shape[0] != G:
+            raise ValueError("textreid_amd.evaluation.topk_rows: mask must be a bool or uint8 tensor of shape [G = %d]" % G)
+        if mask.device != dev:
+            raise ValueError("textreid_amd.evaluation.topk_rows: sim is on %s; got a mask on %s" % (dev, mask.device))
+        m = mask.contiguous()
+        words = torch.empty((G + 31) // 32, dtype=torch.int32, device=dev)
+        call("trid_index_pack_mask_u32", None, _p(m), G, _p(words), words.numel(), stream())
+    vals = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    cols = torch.empty(Q, k, dtype=torch.int64, device=dev)
+    _deep_topk(_p(sim), ld_q, ld_g, Q, G, k, words, vals, cols)
+    return vals, cols
+
+
 def rank(similarity, q_pids, g_pids, topk=(1, 5, 10), get_mAP=True):
+    """CMC (and mAP) of a given [Q, G] similarity matrix (evaluation.py:11-37).  get_mAP=False keeps max(topk) columns per query:
+    up to 16 by trid_topk_rows_f32, up to 1024 by trid_topk_rows_deep_f32, beyond that a slice of the full argsort - one order
+    (value descending, then column ascending) on every route."""
     if not similarity.is_cuda:
         raise RuntimeError("textreid_amd.evaluation.rank runs on the HIP kernel library only (CUDA tensors); no CPU fallback")
     dev = similarity.device
@@ -46,7 +98,8 @@ def rank(similarity, q_pids, g_pids, topk=(1, 5, 10), get_mAP=True):
     max_rank = int(max(topk)) if not torch.is_tensor(topk) else int(topk.max())
     sim = similarity.contiguous().float()
     Q, G = sim.shape
-    if get_mAP:
+    full_sort = get_mAP or max_rank > MAX_DEEP_TOPK
+    if full_sort:
         indices = torch.empty(Q, G, dtype=torch.int64, device=dev)
         # rows beyond the in-LDS sort (G > 16384, e.g. ICFG-PEDES i2t) go through a segmented radix sort in a workspace;
         # row batches keep Q*G below the sort's 2^31-item limit
@@ -56,10 +109,15 @@ def rank(similarity, q_pids, g_pids, topk=(1, 5, 10), get_mAP=True):
             nws = ops.L.load().trid_argsort_ws_bytes(nq, G)
             ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws > 0 else None
             call("trid_argsort_rows_desc_f32", _p(sim[q0:]), G, nq, G, _p(indices[q0:]), _p(ws), nws, stream())
+        if not get_mAP:  # (max(topk) beyond the deep select: the first max_rank columns of the same order)
+            indices = indices[:, :max_rank].contiguous()
     else:
         vals = torch.empty(Q, max_rank, dtype=torch.float32, device=dev)
         indices = torch.empty(Q, max_rank, dtype=torch.int64, device=dev)
-        call("trid_topk_rows_f32", _p(sim), G, Q, G, max_rank, _p(vals), _p(indices), stream())
+        if max_rank <= MAX_TOPK:
+            call("trid_topk_rows_f32", _p(sim), G, Q, G, max_rank, _p(vals), _p(indices), stream())
+        else:
+            _deep_topk(_p(sim), G, 1, Q, G, max_rank, None, vals, indices)
     return _metrics(indices, q_pids, g_pids, topk_t, get_mAP)
 
 

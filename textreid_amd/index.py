@@ -41,24 +41,34 @@ pids = equal ids), derived state like the mask words: a cached buffer, rebuilt b
 masked row is never a representative, a pid without allowed rows is absent.  The number of distinct pids is never read back: a
 query with fewer than k of them ends in ``(-inf, -1, -1)`` slots.  More than 32 queries run in panels of 32.
 
+``shortlist`` is the deep counterpart of ``search``: the exact top-k of the allowed rows for k up to ``MAX_SHORTLIST_K`` = 1024 (a results
+page, 100-1000 candidates for a second-stage matcher), any number of queries in panels of 32.  ``search`` and ``search_pids`` stay at
+k <= 16, the length of the one-pass kernel's per-lane lists, which do not stretch: a 1024-deep list does not fit in registers.
+``shortlist`` selects from the DENSE product instead - ``trid_gemm_p16`` of the index's own operands (P16 gallery as A, the zero-padded
+query panel as B, unit scale), to which the one-pass kernel's similarities are bit-identical, so ``shortlist(k <= 16)`` equals ``search``
+bit for bit - followed by ``trid_topk_rows_deep_f32`` (csrc/topk_deep.hip) with the same allow words.  Memory: a
+score buffer of ``len * cols * 4`` bytes cached on the index and grown with it (cols = 32, or 64 if the tile kernel declines 32 columns:
+128 MB at 1e6 rows) plus the select workspace (``trid_topk_rows_deep_ws_bytes``: 3 MB at k = 100, 192 MB at k = 1024 for 1e6 rows).
+
 An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
 A recorded search answers against the gallery as it stood at the capture (row count, storage and tombstones are part of the
 recording): record again after ``add`` / ``remove`` / ``compact``.
 
-Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
+Not built: ``search_pids`` beyond k = 16, gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output).
 """
 
 import torch
 
 from . import ops
-from .evaluation import MAX_P16_ROWS, _Operands
+from .evaluation import MAX_DEEP_TOPK, MAX_P16_ROWS, _deep_topk, _Operands
 from .ops import _p, call, stream
 
 DIM = 256
 MAX_ROWS = MAX_P16_ROWS   # the 31-bit byte offsets of the P16 retrieval kernels: rows * 1024 < 2^31 (2**21 - 1)
 SMALL_Q = 32              # the panel width of trid_index_search_p16
-MAX_K = 16
+MAX_K = 16                # search / search_pids: the per-lane lists of the one-pass kernel
+MAX_SHORTLIST_K = MAX_DEEP_TOPK  # shortlist: the deep select over the dense score buffer (1024)
 
 
 def _need_cuda(name, t):
@@ -332,13 +342,10 @@ class GalleryIndex:
             self._gids_ok = True
         return buf
 
-    def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None, gids=None):
-        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read.
-        words: the packed allow bits (the masked kernel); None: every row may be returned.  gids: the rows' group ids (the
-        distinct kernel: at most one row per group)."""
-        Q, G = x.shape[0], self._n
-        L = ops.L.load()
-        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
+    def _query_panel(self, x, normalize, need):
+        """Q <= 32 queries -> (the cached zero-padded P16 panel [32, 256] holding them, packed with the unit scalar; the rest of the
+        cached workspace, >= need bytes)"""
+        Q = x.shape[0]
         q16, qn, inv, lists = self._workspace(need)
         if normalize:
             call("trid_l2norm_rows_f32", _p(x), _p(qn), _p(inv), Q, self.dim, 1e-12, stream())
@@ -347,6 +354,16 @@ class GalleryIndex:
             q16[Q : self._panel_rows].zero_()
         self._panel_rows = Q
         call("trid_p16_pack_f32", _p(x), Q, self.dim, self.dim, _p(self._unit), _p(q16), 1, stream())
+        return q16, lists
+
+    def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None, gids=None):
+        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read.
+        words: the packed allow bits (the masked kernel); None: every row may be returned.  gids: the rows' group ids (the
+        distinct kernel: at most one row per group)."""
+        Q, G = x.shape[0], self._n
+        L = ops.L.load()
+        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
+        q16, lists = self._query_panel(x, normalize, need)
         if gids is not None:
             call("trid_index_search_distinct_p16", _p(q16), _p(self._p16), _p(self._unit), _p(gids), None if words is None else _p(words), Q, G, k, 0,
                  _p(vals), _p(rows), _p(lists), workgroups, stream())
@@ -355,8 +372,9 @@ class GalleryIndex:
         else:
             call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
 
-    def _check_search(self, name, queries, k, mask, need_pids=False):
-        """the argument rules search and search_pids share, in the order the messages are promised -> the queries, fp32 contiguous"""
+    def _check_search(self, name, queries, k, mask, need_pids=False, max_k=MAX_K):
+        """the argument rules search, search_pids and shortlist share, in the order the messages are promised -> the queries, fp32
+        contiguous"""
         if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError("GalleryIndex.%s: expected a [Q, %d] tensor" % (name, self.dim))
         if need_pids and not self._has_pids:
@@ -364,8 +382,8 @@ class GalleryIndex:
         G = self._n
         if G == 0:
             raise ValueError("GalleryIndex.%s: the index is empty" % name)
-        if k < 1 or k > MAX_K or k > G:
-            raise ValueError("GalleryIndex.%s: k must be in [1, %d] and <= len(index) = %d; got %d" % (name, MAX_K, G, k))
+        if k < 1 or k > max_k or k > G:
+            raise ValueError("GalleryIndex.%s: k must be in [1, %d] and <= len(index) = %d; got %d" % (name, max_k, G, k))
         if mask is not None:
             if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
                 raise ValueError("GalleryIndex.%s: mask must be a bool or uint8 tensor; got %s" % (name, mask.dtype if torch.is_tensor(mask) else type(mask)))
@@ -427,6 +445,66 @@ class GalleryIndex:
             self._search_small(x[at : at + SMALL_Q], k, normalize, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], words=words, gids=gids)
         pids = self._pids[:G][rows].masked_fill_(rows < 0, -1)  # (a short slot's -1 indexes the last row: in range, then overwritten)
         return vals, rows, pids
+
+    # ------------------------------------------------------------------ shortlist
+    def _score_buffer(self, cols):
+        """the dense product's output, fp32 [capacity, cols]: cached on the index and grown with it"""
+        buf = self._ws.get("scores")
+        if buf is None or buf.shape[0] < self._n or buf.shape[1] != cols:
+            buf = torch.empty(self.capacity, cols, dtype=torch.float32, device=self._rows.device)
+            self._ws["scores"] = buf
+        return buf
+
+    def _dense_scores(self, q16):
+        """-> scores [capacity, cols], rows < len written: trid_gemm_p16 with the P16 gallery as A and the zero-padded query panel as
+        B, both at the unit scale.  cols is 32, the width of the search panel - or 64 once the tile kernel has declined 32 columns
+        (the first call finds out, outside any capture; the 32 panel rows are then copied into a zero-padded panel of 64)."""
+        G = self._n
+        gallery = ops.P16(self._p16[:G], self._unit)
+        if self._ws.get("cols", SMALL_Q) == SMALL_Q:
+            scores = self._score_buffer(SMALL_Q)
+            try:
+                ops.gemm_p16(gallery, ops.P16(q16, self._unit), scores, G, SMALL_Q, self.dim, SMALL_Q)
+                return scores
+            except RuntimeError:
+                self._ws["cols"] = 2 * SMALL_Q
+        cols = 2 * SMALL_Q
+        wide = self._ws.get("panel_wide")
+        if wide is None:
+            wide = torch.zeros(cols, self.dim, dtype=torch.float32, device=self._rows.device)
+            self._ws["panel_wide"] = wide
+        wide[:SMALL_Q].copy_(q16)
+        scores = self._score_buffer(cols)
+        ops.gemm_p16(gallery, ops.P16(wide, self._unit), scores, G, cols, self.dim, cols)
+        return scores
+
+    def shortlist(self, queries, k=100, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64): the exact k best allowed rows of every query for 1 <= k <= MAX_SHORTLIST_K = 1024,
+        value descending then row ascending - the deep counterpart of search (a results page, candidates for a second stage).
+        Per panel of 32 queries: the dense trid_gemm_p16 product of the index's own operands (P16 gallery as A, the zero-padded
+        query panel as B, unit scale) into the cached score buffer, then trid_topk_rows_deep_f32 over it with the allow words of
+        ``live & mask``.  The one-pass kernel's similarities are bit-identical to that product, so shortlist(k <= 16) equals search
+        bit for bit.  queries, normalize, mask: as search (no mask: k <= live_count; with a mask nothing is read back and a query
+        with fewer than k allowed rows ends in (-inf, -1) slots).  No host read; after one eager call (which builds the score
+        buffer and the workspaces) nothing is allocated but the outputs, so it can be captured with torch.cuda.graph: a replay
+        reads the queries' and the mask's contents at replay time; record again after add / remove / compact."""
+        x = self._check_search("shortlist", queries, k, mask, max_k=MAX_SHORTLIST_K)
+        Q, G = x.shape[0], self._n
+        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
+        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        L = ops.L.load()
+        nws = L.trid_topk_rows_deep_ws_bytes(SMALL_Q, G, k, 0)
+        ws = self._ws.get("deep")
+        if ws is None or ws.numel() < nws:
+            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+            self._ws["deep"] = ws
+        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
+            part = x[at : at + SMALL_Q]
+            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
+            scores = self._dense_scores(q16)
+            _deep_topk(_p(scores), 1, scores.shape[1], part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
+        return vals, rows
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):

@@ -7,7 +7,7 @@ Under torch.distributed.run with more than one rank --map times the SHARDED form
 positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
-usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]]
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -18,7 +18,11 @@ over the same gallery from which the fraction F (default 0.1) of the rows was re
 for Q > 32).  Each Q entry gains index_masked_ms and masked_over_index = its median over the unmasked index search's median.
 --distinct [M]: a further form, index_distinct, timed in the same process alternating with the others: GalleryIndex.search_pids on an
 index over the same gallery with M rows per pid (default 4; pid = a fixed random permutation of the rows // M: the distinct one-pass
-kernel, panels of 32 queries for Q > 32).  Each Q entry gains index_distinct_ms and distinct_over_index."""
+kernel, panels of 32 queries for Q > 32).  Each Q entry gains index_distinct_ms and distinct_over_index.
+--deep K [K ...]: GalleryIndex.shortlist(k=K) for each K (17 .. 1024 is the point; any 1 .. 1024 runs) and the k = 16 search of the same
+index, timed in the same process alternating with the others.  Each Q entry gains index_k16_ms, shortlist_ms {K: median, min, max},
+shortlist_over_index {K: its median over the k = 16 search's median} and shortlist_split_ms {K: {entry point: ms}}: one more call
+with an event pair around every library call (the dense product, the deep select, the query packing), summed per entry point."""
 import json, os, sys, time
 import torch
 
@@ -39,6 +43,14 @@ def index_main(argv):
         given = i + 1 < len(argv) and not argv[i + 1].startswith("--")
         distinct = int(argv[i + 1]) if given else 4
         argv = argv[:i] + argv[i + (2 if given else 1):]
+    deep = []
+    if "--deep" in argv:  # (every bare number after --deep is a K, up to the next option)
+        i = argv.index("--deep")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            deep.append(int(argv[j]))
+            j += 1
+        argv = argv[:i] + argv[j:]
     masked = None
     if "--masked" in argv:
         i = argv.index("--masked")
@@ -91,6 +103,10 @@ def index_main(argv):
             forms["index_masked"] = (lambda: idx_m.search(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx_m._search_small(q_raw, K, True, out_v, out_r, wg, idx_m._mask_words(None)))
         if idx_d is not None:
             forms["index_distinct"] = (lambda: idx_d.search_pids(q_raw, K)) if (wg == 0 or Q > 32) else (lambda: idx_d._search_small(q_raw, K, True, out_v, out_r, wg, None, idx_d._group_ids()))
+        if deep:
+            forms["index_k16"] = lambda: idx.search(q_raw, 16)
+        for kd in deep:
+            forms["shortlist_k%d" % kd] = lambda kd=kd: idx.shortlist(q_raw, kd)
         for fn in forms.values():
             for _ in range(WARM):
                 fn()
@@ -115,6 +131,28 @@ def index_main(argv):
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
         if idx_d is not None:
             ent["distinct_over_index"] = ent["index_distinct_ms"]["median"] / ent["index_ms"]["median"]
+        if deep:
+            from textreid_amd import lib as LIB
+
+            ent["shortlist_ms"] = {str(kd): ent.pop("shortlist_k%d_ms" % kd) for kd in deep}
+            ent["shortlist_over_index"] = {str(kd): ent["shortlist_ms"][str(kd)]["median"] / ent["index_k16_ms"]["median"] for kd in deep}
+            ent["shortlist_split_ms"] = {}
+            for kd in deep:
+                torch.cuda.synchronize()
+                LIB.TRACE = []
+                idx.shortlist(q_raw, kd)
+                torch.cuda.synchronize()
+                trace, LIB.TRACE = LIB.TRACE, None
+                split = {}
+                for name, _, e0, e1 in trace:
+                    split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
+                ent["shortlist_split_ms"][str(kd)] = split
+            if Q <= 32:  # the P16 gallery read once, the score buffer written once and read once
+                cols = idx._ws["scores"].shape[1]
+                ent["shortlist_bytes"] = G * 1024 + 2 * G * cols * 4
+                ent["shortlist_floor_ms"] = ent["shortlist_bytes"] / HBM * 1e3
+            a16, s16 = idx.search(q_raw, 16), idx.shortlist(q_raw, 16)
+            ent["shortlist16_equals_search"] = bool(torch.equal(a16[1], s16[1]) and torch.equal(a16[0].view(torch.int32), s16[0].view(torch.int32))) if Q <= 32 else None
         a, b = idx.search(q_raw, K), E.similarity_topk(q_raw, g_raw, K)
         ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
         ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
