@@ -818,6 +818,20 @@ int trid_topk_rows_deep_chunk(int k);
 long long trid_topk_rows_deep_ws_bytes(int Q, int G, int k, int chunk);
 int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, int Q, int G, int k, const uint32_t* mask_words,
                             long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk, void* stream);
+/* The k-reciprocal bonus of GalleryIndex.search_reranked (csrc/index_rerank.hip), IN PLACE on a score matrix addressed as in the deep
+ * select above (element (q, g) = scores[q * ld_q + g * ld_g], the [G, cols] product and row-major [Q, G] both work, aliasing strides
+ * are refused), between the dense product and the select.  qnn [Q, n] int64: each query's own neighbour rows (the out_idx of a deep
+ * select with k = n; -1 = absent slot); gnn [G, n] int32: the stored neighbour list of every gallery row (entries below 0 match
+ * nothing).  Lists hold distinct rows.  nq(q) = entries >= 0 of qnn[q]; c(q, g) = equal pairs qnn[q, t] == gnn[g, u] >= 0.  Where row
+ * g is allowed (mask_words as in the deep select, bits of rows >= G ignored, NULL = every row) and c > 0:
+ *   scores[q, g] = scores[q, g] + bonus(nq, c),   bonus(nq, c) = (alpha * (float)c) / (float)(nq + n - c),
+ * every operation rounded to fp32 - for nq == n the expression of trid_jaccard_add_f32.  The (n + 1) x (n + 1) bonus table is formed
+ * on the host in plain float arithmetic and passed by value: the device does one fp32 add.  Every other element - c == 0, a
+ * disallowed row, columns >= Q, rows >= G, the gaps between strides - keeps its bits and is not written.  Q >= 1 (groups of 32
+ * queries on the grid's second dimension, at most 65535 of them), 1 <= n <= 8, n <= G; scores / gnn / mask_words 4-byte, qnn 8-byte
+ * aligned.  No host read, no allocation, one launch: it can be captured. */
+int trid_index_rerank_add_f32(float* scores, long long ld_q, long long ld_g, int Q, int G, const int64_t* qnn, const int32_t* gnn,
+                              int n, float alpha, const uint32_t* mask_words, void* stream);
 /* per-row full descending argsort (rank(get_mAP=True), evaluation.py:14), ties -> lower column first.  G <= 16384:
  * one in-LDS bitonic sort per row, no workspace (ws may be NULL).  Larger rows: packed keys + rocPRIM segmented radix
  * sort in the caller's workspace of trid_argsort_ws_bytes(Q, G) bytes (256-byte aligned; 0 = none needed, or Q*G >= 2^31:

@@ -50,12 +50,36 @@ bit for bit - followed by ``trid_topk_rows_deep_f32`` (csrc/topk_deep.hip, DESIG
 score buffer of ``len * cols * 4`` bytes cached on the index and grown with it (cols = 32, or 64 if the tile kernel declines 32 columns:
 128 MB at 1e6 rows) plus the select workspace (``trid_topk_rows_deep_ws_bytes``: 3 MB at k = 100, 192 MB at k = 1024 for 1e6 rows).
 
+``search_reranked`` is the second stage on the index itself: the exact top-k (k <= 1024) by the RE-RANKED score the evaluation's
+``rerank=True`` tables measure, ``similarity + alpha * Jaccard(N(query), N(row))`` over neighbour lists of n rows (DESIGN.md section
+7i).  It needs the neighbour graph, derived state like the mask words and the group ids but built on request:
+  * ``build_neighbours(n=5)``: ``N(j)`` of a live row j = the n best live rows for row j's own embedding as the query, in the order
+    above - so j itself normally comes first, an exact duplicate with a lower row number before it.  1 <= n <= 8, n <= live_count.
+    The similarities are those of the dense ``trid_gemm_p16`` product: panels of 32 consecutive gallery rows run as the query panel of
+    the one-pass kernel (k = n), full panels in place in the P16 storage, the ragged last one through the cached zero-padded panel;
+    with tombstones the masked form.  ``ceil(len / 32)`` gallery passes: quadratic in ``len`` (n = 5 on one MI355X: 0.29 s at 1e5
+    rows, 7.7 s at 1e6).  Stored as int32 ``[capacity, n]``,
+    -1 in every slot of a removed row; read-only face ``neighbours`` (int32 [len, n]; None when no lists are held: never built, or
+    dropped by a ``compact`` that renumbered the rows) and ``neighbours_current``.
+  * ``add``, ``remove`` (when it removed something), ``compact`` (when it dropped something) and ``load_state_dict`` without a graph
+    make the graph stale; ``search_reranked`` then raises and names ``build_neighbours``.  A ``mask=`` never makes it stale: the lists
+    are a property of the stored gallery, the mask of one question.  ``state_dict()["neighbours"]`` carries a current graph.
+  * per panel of 32 queries: the dense product of ``shortlist``; a deep select with k = n and the allow words of ``live & mask``
+    gives the query's own list (its n best ALLOWED rows; fewer allowed rows leave -1 slots and nq < n);
+    ``trid_index_rerank_add_f32`` (csrc/index_rerank.hip) adds ``(alpha * c) / (nq + n - c)`` in place where the lists share c > 0
+    rows; a second deep select with k over every allowed row of the modified buffer - exact by construction.  ``alpha = 0.0``
+    skips the pass and equals ``shortlist`` bit for bit.  G = 1e6, k = 100: 0.50 / 0.80 / 1.29 ms at Q = 1 / 8 / 32 against
+    ``shortlist``'s 0.44 / 0.60 / 0.97 ms; the extra select is the cost, the bonus pass takes 0.01-0.05 ms.
+
 An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
-A recorded search answers against the gallery as it stood at the capture (row count, storage and tombstones are part of the
-recording): record again after ``add`` / ``remove`` / ``compact``.
+A recorded search answers against the gallery as it stood at the capture (row count, storage, tombstones and neighbour graph are
+part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours``.
 
 Not built: ``search_pids`` beyond k = 16, gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
-image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output).
+image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); incremental maintenance
+of the neighbour graph on ``add`` (merging a new row into the old lists needs their stored VALUES and a second query direction -
+old rows against the new panel - whose bit-identity to the definition above would have to be shown first; ``add`` makes the graph
+stale instead); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).
 """
 
 import torch
@@ -68,7 +92,8 @@ DIM = 256
 MAX_ROWS = MAX_P16_ROWS   # the 31-bit byte offsets of the P16 retrieval kernels: rows * 1024 < 2^31 (2**21 - 1)
 SMALL_Q = 32              # the panel width of trid_index_search_p16
 MAX_K = 16                # search / search_pids: the per-lane lists of the one-pass kernel
-MAX_SHORTLIST_K = MAX_DEEP_TOPK  # shortlist: the deep select over the dense score buffer (1024)
+MAX_SHORTLIST_K = MAX_DEEP_TOPK  # shortlist / search_reranked: the deep select over the dense score buffer (1024)
+MAX_NEIGHBOURS = 8        # build_neighbours: the list length of trid_index_rerank_add_f32 (and of trid_jaccard_add_f32)
 
 
 def _need_cuda(name, t):
@@ -110,6 +135,8 @@ class GalleryIndex:
         self._dead = 0      # removed rows among the first len (host count)
         self._words_ok = False  # the cached mask words of the tombstones are current
         self._gids_ok = False   # the cached group ids of the pids are current
+        self._nn = None     # int32 [capacity, n]: the neighbour graph (build_neighbours), -1 in every slot of a removed row
+        self._nn_ok = False     # the graph is current: no add / remove / compact since it was built or loaded
         self._has_pids = None
         self._unit = None   # device scalar 1.0: the amax every row and every query is packed with
         self._ws = {}       # the cached workspace of the small-batch search
@@ -155,6 +182,17 @@ class GalleryIndex:
         """rows not removed (a host int)"""
         return self._n - self._dead
 
+    @property
+    def neighbours(self):
+        """int32 [len, n]: the neighbour lists as build_neighbours (or load_state_dict) left them, -1 in every slot of a row that was
+        removed then or appended since (a view of the storage: read-only); None when no lists are held"""
+        return None if self._nn is None else self._nn[: self._n]
+
+    @property
+    def neighbours_current(self):
+        """the lists describe the gallery as it stands: search_reranked takes them"""
+        return self._nn is not None and self._nn_ok
+
     def _reserve(self, total, device):
         if self._rows is not None and self._rows.device != device:
             raise ValueError("GalleryIndex: the index lives on %s; got a tensor on %s" % (self._rows.device, device))
@@ -173,6 +211,10 @@ class GalleryIndex:
             live[: self._n].copy_(self._live[: self._n])
         self._rows, self._p16, self._pids, self._live = rows, p16, pids, live
         self._words_ok = self._gids_ok = False
+        if self._nn is not None:  # (the lists grow with the storage like the other workspaces; growth alone changes nothing in them)
+            nn = torch.full((new_cap, self._nn.shape[1]), -1, dtype=torch.int32, device=device)
+            nn[: self._n].copy_(self._nn[: self._n])
+            self._nn = nn
         if self._unit is None:
             self._unit = torch.ones(1, dtype=torch.float32, device=device)
 
@@ -223,6 +265,9 @@ class GalleryIndex:
         self._live[first : first + n] = True
         self._n = first + n
         self._words_ok = self._gids_ok = False
+        if self._nn is not None:  # (no list knows the new rows and they have none: the graph is stale until the next build)
+            self._nn[first : first + n] = -1
+        self._nn_ok = False
         return first
 
     # ------------------------------------------------------------------ removal
@@ -255,6 +300,7 @@ class GalleryIndex:
             live &= ~sel
             self._dead += newly
             self._words_ok = False
+            self._nn_ok = False  # (lists that held a removed row are one live neighbour short)
         return newly
 
     def compact(self):
@@ -281,6 +327,7 @@ class GalleryIndex:
         self._rows, self._p16, self._pids = rows, p16, pids
         self._live = torch.ones(cap, dtype=torch.bool, device=dev)
         self._n, self._dead, self._words_ok, self._gids_ok = m, 0, False, False
+        self._nn, self._nn_ok = None, False  # (the lists hold the old row numbers: dropped, not kept as a trap)
         if m == 0:
             self._has_pids = None
         return new_of
@@ -372,9 +419,9 @@ class GalleryIndex:
         else:
             call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
 
-    def _check_search(self, name, queries, k, mask, need_pids=False, max_k=MAX_K):
-        """the argument rules search, search_pids and shortlist share, in the order the messages are promised -> the queries, fp32
-        contiguous"""
+    def _check_search(self, name, queries, k, mask, need_pids=False, max_k=MAX_K, need_graph=False):
+        """the argument rules search, search_pids, shortlist and search_reranked share, in the order the messages are promised -> the
+        queries, fp32 contiguous.  need_graph: a current neighbour graph, asked for after the argument rules and before the device's"""
         if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError("GalleryIndex.%s: expected a [Q, %d] tensor" % (name, self.dim))
         if need_pids and not self._has_pids:
@@ -393,6 +440,9 @@ class GalleryIndex:
             raise ValueError("GalleryIndex.%s: k must be <= live_count = %d (%d of %d rows were removed); got %d" % (name, self.live_count, self._dead, G, k))
         if queries.shape[0] == 0:
             raise ValueError("GalleryIndex.%s: no queries" % name)
+        if need_graph and not self.neighbours_current:
+            raise RuntimeError("GalleryIndex.%s: the neighbour graph is %s; call build_neighbours() first" % (
+                name, "absent" if self._nn is None else "stale (add / remove / compact / load_state_dict since it was built)"))
         _need_cuda(name, queries)
         x = queries.contiguous().float()
         if x.device != self._rows.device:
@@ -478,6 +528,16 @@ class GalleryIndex:
         ops.gemm_p16(gallery, ops.P16(wide, self._unit), scores, G, cols, self.dim, cols)
         return scores
 
+    def _deep_workspace(self, *ks):
+        """the cached workspace of the deep select, large enough for a panel of 32 queries at every k given"""
+        L = ops.L.load()
+        nws = max(L.trid_topk_rows_deep_ws_bytes(SMALL_Q, self._n, k, 0) for k in ks)
+        ws = self._ws.get("deep")
+        if ws is None or ws.numel() < nws:
+            ws = torch.empty(nws, dtype=torch.uint8, device=self._rows.device)
+            self._ws["deep"] = ws
+        return ws
+
     def shortlist(self, queries, k=100, normalize=True, mask=None):
         """-> (values [Q,k] f32, rows [Q,k] i64): the exact k best allowed rows of every query for 1 <= k <= MAX_SHORTLIST_K = 1024,
         value descending then row ascending - the deep counterpart of search (a results page, candidates for a second stage).
@@ -494,11 +554,7 @@ class GalleryIndex:
         rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
         words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
         L = ops.L.load()
-        nws = L.trid_topk_rows_deep_ws_bytes(SMALL_Q, G, k, 0)
-        ws = self._ws.get("deep")
-        if ws is None or ws.numel() < nws:
-            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-            self._ws["deep"] = ws
+        ws = self._deep_workspace(k)
         for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
             part = x[at : at + SMALL_Q]
             q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
@@ -506,29 +562,126 @@ class GalleryIndex:
             _deep_topk(_p(scores), 1, scores.shape[1], part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
         return vals, rows
 
+    # ------------------------------------------------------------------ neighbour graph and re-ranked search
+    def build_neighbours(self, n=5):
+        """Build the neighbour graph search_reranked needs: for every live row j, N(j) = the n best live rows for row j's own
+        embedding as the query (value descending, then row ascending: j itself first unless an exact duplicate has a lower row
+        number); -1 in every slot of a removed row.  1 <= n <= 8, n <= live_count.  ceil(len / 32) passes of the one-pass kernel
+        (the masked form with the cached tombstone words once rows were removed), panels of 32 consecutive gallery rows as the
+        query panel - in place in the P16 storage, the ragged last one through the cached zero-padded panel - so the similarities
+        are bit-identical to the dense trid_gemm_p16 product of the index's own operands.  Quadratic in len; no host read."""
+        if n < 1 or n > MAX_NEIGHBOURS:
+            raise ValueError("GalleryIndex.build_neighbours: n must be in [1, %d]; got %d" % (MAX_NEIGHBOURS, n))
+        G = self._n
+        if G == 0:
+            raise ValueError("GalleryIndex.build_neighbours: the index is empty")
+        if n > self.live_count:
+            raise ValueError("GalleryIndex.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
+        L = ops.L.load()
+        tail = G % SMALL_Q
+        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, SMALL_Q, n, 0),
+                   L.trid_index_search_ws_bytes(G, tail, n, 0) if tail else 0)
+        q16, _, _, lists = self._workspace(need)
+        words = self._mask_words(None) if self._dead else None
+        dev = self._rows.device
+        vals = torch.empty(SMALL_Q, n, dtype=torch.float32, device=dev)
+        found = torch.empty(G, n, dtype=torch.int64, device=dev)
+        for at in range(0, G, SMALL_Q):
+            Q = min(SMALL_Q, G - at)
+            if Q == SMALL_Q:  # (the stored rows ARE a panel: packed with the unit scalar, 1024 bytes per row, 16-byte aligned)
+                panel = self._p16[at : at + SMALL_Q]
+            else:
+                q16.view(torch.int32)[:Q].copy_(self._p16.view(torch.int32)[at : at + Q])
+                if Q < self._panel_rows:
+                    q16[Q : self._panel_rows].zero_()
+                self._panel_rows = Q
+                panel = q16
+            if words is None:
+                call("trid_index_search_p16", _p(panel), _p(self._p16), _p(self._unit), Q, G, n, 0, _p(vals), _p(found[at:]), _p(lists), 0, stream())
+            else:
+                call("trid_index_search_masked_p16", _p(panel), _p(self._p16), _p(self._unit), _p(words), Q, G, n, 0, _p(vals), _p(found[at:]),
+                     _p(lists), 0, stream())
+        if self._nn is None or self._nn.shape[1] != n or self._nn.shape[0] < self.capacity:
+            self._nn = torch.empty(self.capacity, n, dtype=torch.int32, device=dev)
+        self._nn[:G].copy_(found)
+        self._nn[G:] = -1
+        if self._dead:
+            self._nn[:G].masked_fill_(~self._live[:G, None], -1)
+        self._nn_ok = True
+
+    def search_reranked(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64): the exact k best allowed rows of every query by RE-RANKED score, similarity +
+        (alpha * c) / (nq + n - c) with c = rows the query's own neighbour list and the row's stored list share, n = the graph's
+        list length, nq = the query's list length (n unless fewer rows are allowed) - for nq == n alpha times the Jaccard index of
+        the two lists, the term of evaluation.k_reciprocal.  1 <= k <= MAX_SHORTLIST_K = 1024, value descending then row ascending.
+        Needs a current graph (build_neighbours; RuntimeError otherwise).  Per panel of 32 queries: the dense product of shortlist
+        into the cached score buffer; a deep select with k = n over the allowed rows (``live & mask``) = the query's own list;
+        trid_index_rerank_add_f32 in place on the buffer; a deep select with k over every allowed row of the modified buffer - so
+        the result is exact, not a re-ordered shortlist.  alpha == 0.0 skips the bonus (and the select that only feeds it) and equals shortlist bit for bit.  queries,
+        normalize, mask: as shortlist.  No host read; after one eager call nothing is allocated but the outputs and the queries'
+        lists, so it can be captured with torch.cuda.graph; record again after add / remove / compact / build_neighbours."""
+        x = self._check_search("search_reranked", queries, k, mask, max_k=MAX_SHORTLIST_K, need_graph=True)
+        alpha = float(alpha)
+        Q, G, n = x.shape[0], self._n, self._nn.shape[1]
+        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
+        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        L = ops.L.load()
+        ws = self._deep_workspace(k, n)
+        if alpha != 0.0:
+            qnn = torch.empty(min(Q, SMALL_Q), n, dtype=torch.int64, device=x.device)
+            qval = torch.empty(min(Q, SMALL_Q), n, dtype=torch.float32, device=x.device)
+        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
+            part = x[at : at + SMALL_Q]
+            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
+            scores = self._dense_scores(q16)
+            cols = scores.shape[1]
+            if alpha != 0.0:
+                _deep_topk(_p(scores), 1, cols, part.shape[0], G, n, words, qval, qnn, ws=ws)
+                call("trid_index_rerank_add_f32", _p(scores), 1, cols, part.shape[0], G, _p(qnn), _p(self._nn), n, alpha, _p(words), stream())
+            _deep_topk(_p(scores), 1, cols, part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
+        return vals, rows
+
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
         """the normalised fp32 rows, the pids (None without) and the liveness (bool [len]; None when nothing was removed); P16 is
-        re-derived on load"""
+        re-derived on load; "neighbours": the int32 [len, n] lists of a CURRENT neighbour graph, None otherwise"""
         return {"rows": None if self._rows is None else self._rows[: self._n].clone(),
                 "pids": None if not self._has_pids else self._pids[: self._n].clone(),
-                "live": None if not self._dead else self._live[: self._n].clone()}
+                "live": None if not self._dead else self._live[: self._n].clone(),
+                "neighbours": None if not self.neighbours_current or self._n == 0 else self._nn[: self._n].clone()}
+
+    @staticmethod
+    def _check_neighbours(nn, rows):
+        """the lists of a state dict: int32 [rows, n], 1 <= n <= 8, values in [-1, rows) (one host read: load is not the latency path)"""
+        if not torch.is_tensor(nn) or nn.dtype != torch.int32 or nn.dim() != 2 or nn.shape[0] != rows or not 1 <= nn.shape[1] <= MAX_NEIGHBOURS:
+            raise ValueError("GalleryIndex.load_state_dict: neighbours must be an int32 [%d, n] tensor with 1 <= n <= %d; got %s" % (
+                rows, MAX_NEIGHBOURS, "%s %s" % (nn.dtype, tuple(nn.shape)) if torch.is_tensor(nn) else type(nn)))
+        lo, hi = int(nn.min()), int(nn.max())
+        if lo < -1 or hi >= rows:
+            raise ValueError("GalleryIndex.load_state_dict: neighbours must hold rows in [-1, %d); got %d" % (rows, lo if lo < -1 else hi))
 
     def load_state_dict(self, sd):
         """Replace the contents.  The rows are taken as they are (already normalised: no second normalisation) and re-packed.  A
-        state dict without "live" (as written before removal existed) loads as all-live."""
+        state dict without "live" (as written before removal existed) loads as all-live.  "neighbours" present and not None: the
+        lists are adopted as the current neighbour graph; a dict without them loads with no graph."""
         rows = sd["rows"]
         if rows is None or rows.shape[0] == 0:
             self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
+            self._nn, self._nn_ok = None, False
             return
         if rows.shape[0] > MAX_ROWS:
             raise ValueError("GalleryIndex.load_state_dict: at most %d rows; got %d" % (MAX_ROWS, rows.shape[0]))
+        nn = sd.get("neighbours")
+        if nn is not None:
+            self._check_neighbours(nn, rows.shape[0])
         x = self._check_rows("load_state_dict", rows)
         n = x.shape[0]
         live = sd.get("live")
         if live is not None and (not torch.is_tensor(live) or live.numel() != n):
             raise ValueError("GalleryIndex.load_state_dict: live must hold one entry per row (%d)" % n)
         self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
+        self._nn, self._nn_ok = None, False
         self._reserve(n, x.device)
         self._rows[:n].copy_(x)
         self._pack_into(0, n)
@@ -541,3 +694,7 @@ class GalleryIndex:
             self._live[:n].copy_(live.to(x.device).reshape(-1) != 0)
             self._dead = n - int(self._live[:n].sum())
         self._n = n
+        if nn is not None:
+            self._nn = torch.full((self.capacity, nn.shape[1]), -1, dtype=torch.int32, device=x.device)
+            self._nn[:n].copy_(nn.to(x.device))
+            self._nn_ok = True

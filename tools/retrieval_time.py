@@ -7,7 +7,7 @@ Under torch.distributed.run with more than one rank --map times the SHARDED form
 positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
-usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]]
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -22,7 +22,11 @@ kernel, panels of 32 queries for Q > 32).  Each Q entry gains index_distinct_ms 
 --deep K [K ...]: GalleryIndex.shortlist(k=K) for each K (17 .. 1024 is the point; any 1 .. 1024 runs) and the k = 16 search of the same
 index, timed in the same process alternating with the others.  Each Q entry gains index_k16_ms, shortlist_ms {K: median, min, max},
 shortlist_over_index {K: its median over the k = 16 search's median} and shortlist_split_ms {K: {entry point: ms}}: one more call
-with an event pair around every library call (the dense product, the deep select, the query packing), summed per entry point."""
+with an event pair around every library call (the dense product, the deep select, the query packing), summed per entry point.
+--rerank K [K ...]: GalleryIndex.build_neighbours(5) timed once (build_neighbours_ms), then search_reranked(k=K) and shortlist(k=K) of the
+same index for each K, timed in the same process alternating with the others.  Each Q entry gains reranked_ms and reranked_shortlist_ms
+{K: median, min, max}, reranked_over_shortlist {K: ratio of the medians}, reranked_split_ms {K: {entry point: ms}} (the bonus pass is
+trid_index_rerank_add_f32) and bonus_floor_ms: the graph's G * n * 4 bytes read once per panel of 32 queries, at 6.3 TB/s."""
 import json, os, sys, time
 import torch
 
@@ -51,6 +55,14 @@ def index_main(argv):
             deep.append(int(argv[j]))
             j += 1
         argv = argv[:i] + argv[j:]
+    rerank = []
+    if "--rerank" in argv:  # (as --deep: every bare number after it is a K)
+        i = argv.index("--rerank")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            rerank.append(int(argv[j]))
+            j += 1
+        argv = argv[:i] + argv[j:]
     masked = None
     if "--masked" in argv:
         i = argv.index("--masked")
@@ -70,6 +82,12 @@ def index_main(argv):
     torch.cuda.synchronize()
     line = {"G": G, "C": 256, "k": K, "calls": CALLS, "warmup": WARM, "forced_workgroups": wg, "add_ms": (time.perf_counter() - t0) * 1e3, "Q": {}}
     g_unit = idx.rows
+    if rerank:  # the neighbour graph, built once: ceil(G / 32) one-pass searches of the whole gallery
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        idx.build_neighbours(5)
+        torch.cuda.synchronize()
+        line["build_neighbours_ms"], line["neighbours_n"], line["build_panels"] = (time.perf_counter() - t0) * 1e3, 5, (G + 31) // 32
     idx_m = None
     if masked is not None:
         idx_m = GalleryIndex(capacity=G)
@@ -107,6 +125,9 @@ def index_main(argv):
             forms["index_k16"] = lambda: idx.search(q_raw, 16)
         for kd in deep:
             forms["shortlist_k%d" % kd] = lambda kd=kd: idx.shortlist(q_raw, kd)
+        for kr in rerank:
+            forms["shortlist_k%d" % kr] = lambda kr=kr: idx.shortlist(q_raw, kr)
+            forms["reranked_k%d" % kr] = lambda kr=kr: idx.search_reranked(q_raw, kr)
         for fn in forms.values():
             for _ in range(WARM):
                 fn()
@@ -131,6 +152,25 @@ def index_main(argv):
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
         if idx_d is not None:
             ent["distinct_over_index"] = ent["index_distinct_ms"]["median"] / ent["index_ms"]["median"]
+        if rerank:
+            from textreid_amd import lib as LIB
+
+            ent["reranked_ms"] = {str(kr): ent.pop("reranked_k%d_ms" % kr) for kr in rerank}
+            ent["reranked_shortlist_ms"] = {str(kr): ent["shortlist_k%d_ms" % kr] if kr in deep else ent.pop("shortlist_k%d_ms" % kr) for kr in rerank}
+            ent["reranked_over_shortlist"] = {str(kr): ent["reranked_ms"][str(kr)]["median"] / ent["reranked_shortlist_ms"][str(kr)]["median"] for kr in rerank}
+            ent["reranked_split_ms"] = {}
+            for kr in rerank:  # one more call with an event pair around every library call, summed per entry point
+                torch.cuda.synchronize()
+                LIB.TRACE = []
+                idx.search_reranked(q_raw, kr)
+                torch.cuda.synchronize()
+                trace, LIB.TRACE = LIB.TRACE, None
+                split = {}
+                for name, _, e0, e1 in trace:
+                    split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
+                ent["reranked_split_ms"][str(kr)] = split
+            ent["bonus_bytes"] = G * line["neighbours_n"] * 4  # the pass's floor: the graph read once per panel of 32 queries
+            ent["bonus_floor_ms"] = ((Q + 31) // 32) * ent["bonus_bytes"] / HBM * 1e3
         if deep:
             from textreid_amd import lib as LIB
 
