@@ -832,6 +832,21 @@ int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, in
  * aligned.  No host read, no allocation, one launch: it can be captured. */
 int trid_index_rerank_add_f32(float* scores, long long ld_q, long long ld_g, int Q, int G, const int64_t* qnn, const int32_t* gnn,
                               int n, float alpha, const uint32_t* mask_words, void* stream);
+/* The merge step of GalleryIndex.refresh_neighbours (csrc/index_nn_update.hip): the stored neighbour lists nn [*, n] int32 and their
+ * values nn_val [*, n] fp32 of the rows [0, rows) - value descending, then row ascending - take in m candidate rows numbered
+ * cand_first .. cand_first + m - 1, rows <= cand_first: candidates are numbered above every merged row.  cand[j * ld_cand + i] = the
+ * similarity of old row i (as the query) to candidate j; live = uint8 [cand_first + m].  m == 0 with cand == NULL is the pure-removal
+ * pass.  Per row i < rows:
+ *   live[i] == 0: all n slots become (-1, -inf), redo[i] = 0;
+ *   else nn[i, 0] < 0 (a live row no graph has covered) or some entry e >= 0 with live[e] == 0 (an entry >= cand_first + m counts as
+ *     such; nothing is read through it): redo[i] = 1, the list and its values are NOT written - the caller recomputes the row;
+ *   else redo[i] = 0 and every candidate j in ascending order with live[cand_first + j] != 0 is inserted where it comes strictly
+ *     before an entry by value (float comparison: an equal value stays behind the older, lower row), the last entry falls off;
+ *     values move with their rows and keep their bits.
+ * Nothing outside nn / nn_val [0, rows) x [0, n) and redo [0, rows) is written.  1 <= n <= 8, m >= 0, 1 <= rows <= cand_first,
+ * ld_cand >= rows when m > 0, cand / nn / nn_val 4-byte aligned.  No host read, no allocation, one launch. */
+int trid_index_nn_merge_f32(const float* cand, long long ld_cand, int m, int cand_first, int rows, const uint8_t* live, int32_t* nn,
+                            float* nn_val, int n, uint8_t* redo, void* stream);
 /* per-row full descending argsort (rank(get_mAP=True), evaluation.py:14), ties -> lower column first.  G <= 16384:
  * one in-LDS bitonic sort per row, no workspace (ws may be NULL).  Larger rows: packed keys + rocPRIM segmented radix
  * sort in the caller's workspace of trid_argsort_ws_bytes(Q, G) bytes (256-byte aligned; 0 = none needed, or Q*G >= 2^31:

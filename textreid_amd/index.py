@@ -64,6 +64,18 @@ score buffer of ``len * cols * 4`` bytes cached on the index and grown with it (
   * ``add``, ``remove`` (when it removed something), ``compact`` (when it dropped something) and ``load_state_dict`` without a graph
     make the graph stale; ``search_reranked`` then raises and names ``build_neighbours``.  A ``mask=`` never makes it stale: the lists
     are a property of the stored gallery, the mask of one question.  ``state_dict()["neighbours"]`` carries a current graph.
+  * ``refresh_neighbours()`` brings a stale graph up to date EXACTLY - lists and values bit-identical to a rebuild - at the cost of
+    the change, not of the gallery squared.  The build keeps the VALUE of every list entry (fp32
+    ``[capacity, n]``, -inf in every slot of a removed row; ``neighbour_values``, ``state_dict()["neighbour_values"]``) and the graph
+    remembers how many rows it covered.  Old rows against new rows is a second query direction whose values must be those of the
+    definition (old row i as the B panel, new row g as A: ``s(i, g)`` and ``s(g, i)`` differ in the last bits): per group of 32 new
+    rows one ``trid_gemm_p16`` product with the group as A and ALL old P16 rows as B - bit-identical to the narrow products of the
+    build, because an element's accumulation order in the tile kernel depends on neither tile shape nor position - and one
+    ``trid_index_nn_merge_f32`` (csrc/index_nn_update.hip: one old row per lane, branch-free insert into the register-held list).
+    The new rows' own lists come from the build's panel loop over their range; old rows whose list held a removed row are flagged
+    by the merge, read once on the host and recomputed in panels of 32.  ``neighbours_refreshable``: lists and values are both
+    held (not after a ``compact`` that dropped them, not after loading lists without values).  ``compact(keep_neighbours=True)``
+    gathers a current graph to the new row numbers instead of dropping it.
   * per panel of 32 queries: the dense product of ``shortlist``; a deep select with k = n and the allow words of ``live & mask``
     gives the query's own list (its n best ALLOWED rows; fewer allowed rows leave -1 slots and nq < n);
     ``trid_index_rerank_add_f32`` (csrc/index_rerank.hip) adds ``(alpha * c) / (nq + n - c)`` in place where the lists share c > 0
@@ -73,13 +85,12 @@ score buffer of ``len * cols * 4`` bytes cached on the index and grown with it (
 
 An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
 A recorded search answers against the gallery as it stood at the capture (row count, storage, tombstones and neighbour graph are
-part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours``.
+part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours`` / ``refresh_neighbours``.
 
 Not built: ``search_pids`` beyond k = 16, gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
-image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); incremental maintenance
-of the neighbour graph on ``add`` (merging a new row into the old lists needs their stored VALUES and a second query direction -
-old rows against the new panel - whose bit-identity to the definition above would have to be shown first; ``add`` makes the graph
-stale instead); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).
+image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
+or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
+pass); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).
 """
 
 import torch
@@ -137,6 +148,8 @@ class GalleryIndex:
         self._gids_ok = False   # the cached group ids of the pids are current
         self._nn = None     # int32 [capacity, n]: the neighbour graph (build_neighbours), -1 in every slot of a removed row
         self._nn_ok = False     # the graph is current: no add / remove / compact since it was built or loaded
+        self._nn_val = None  # fp32 [capacity, n]: the similarity of every list entry (refresh_neighbours merges by them), -inf in every slot of a removed row
+        self._nn_rows = 0    # rows the graph covered when it was last current: refresh_neighbours treats [_nn_rows, len) as new
         self._has_pids = None
         self._unit = None   # device scalar 1.0: the amax every row and every query is packed with
         self._ws = {}       # the cached workspace of the small-batch search
@@ -193,6 +206,18 @@ class GalleryIndex:
         """the lists describe the gallery as it stands: search_reranked takes them"""
         return self._nn is not None and self._nn_ok
 
+    @property
+    def neighbour_values(self):
+        """fp32 [len, n]: the similarity of every entry of ``neighbours`` (the dense product's own bits), -inf in every slot of a
+        row that was removed then or appended since (a view of the storage: read-only); None when no values are held (no lists, or
+        lists loaded from a state dict without them)"""
+        return None if self._nn is None or self._nn_val is None else self._nn_val[: self._n]
+
+    @property
+    def neighbours_refreshable(self):
+        """lists and their values are both held, with the same n: refresh_neighbours can bring the graph up to date"""
+        return self._nn is not None and self._nn_val is not None and self._nn_val.shape[1] == self._nn.shape[1]
+
     def _reserve(self, total, device):
         if self._rows is not None and self._rows.device != device:
             raise ValueError("GalleryIndex: the index lives on %s; got a tensor on %s" % (self._rows.device, device))
@@ -215,6 +240,10 @@ class GalleryIndex:
             nn = torch.full((new_cap, self._nn.shape[1]), -1, dtype=torch.int32, device=device)
             nn[: self._n].copy_(self._nn[: self._n])
             self._nn = nn
+            if self._nn_val is not None:
+                val = torch.full((new_cap, self._nn_val.shape[1]), float("-inf"), dtype=torch.float32, device=device)
+                val[: self._n].copy_(self._nn_val[: self._n])
+                self._nn_val = val
         if self._unit is None:
             self._unit = torch.ones(1, dtype=torch.float32, device=device)
 
@@ -265,8 +294,10 @@ class GalleryIndex:
         self._live[first : first + n] = True
         self._n = first + n
         self._words_ok = self._gids_ok = False
-        if self._nn is not None:  # (no list knows the new rows and they have none: the graph is stale until the next build)
+        if self._nn is not None:  # (no list knows the new rows and they have none: the graph is stale until the next build or refresh)
             self._nn[first : first + n] = -1
+            if self._nn_val is not None:
+                self._nn_val[first : first + n] = float("-inf")
         self._nn_ok = False
         return first
 
@@ -303,10 +334,13 @@ class GalleryIndex:
             self._nn_ok = False  # (lists that held a removed row are one live neighbour short)
         return newly
 
-    def compact(self):
+    def compact(self, keep_neighbours=False):
         """Drop the removed rows, order kept; -> int64 [old len] on the device, old row -> new row, -1 for a removed row.  Out of
         place: rows, rows_p16 (copied, not re-packed: the fixed unit scale) and pids are gathered into new storage.  Afterwards
-        there are no tombstones and searches run the unmasked path; recorded searches must be recorded again."""
+        there are no tombstones and searches run the unmasked path; recorded searches must be recorded again.
+        keep_neighbours=True with a CURRENT graph: the lists (and their values, when held) of the kept rows are gathered to the new
+        row numbers - a current graph holds live rows only, so every entry has one - and the graph stays current (and refreshable).
+        The default, and a stale graph, drop the lists."""
         n = self._n
         if self._rows is None:
             return torch.empty(0, dtype=torch.int64)
@@ -327,7 +361,17 @@ class GalleryIndex:
         self._rows, self._p16, self._pids = rows, p16, pids
         self._live = torch.ones(cap, dtype=torch.bool, device=dev)
         self._n, self._dead, self._words_ok, self._gids_ok = m, 0, False, False
-        self._nn, self._nn_ok = None, False  # (the lists hold the old row numbers: dropped, not kept as a trap)
+        if keep_neighbours and self.neighbours_current and m:
+            nn = torch.full((cap, self._nn.shape[1]), -1, dtype=torch.int32, device=dev)
+            nn[:m] = new_of[self._nn[keep].long()].int()
+            self._nn = nn
+            if self._nn_val is not None:
+                val = torch.full((cap, self._nn_val.shape[1]), float("-inf"), dtype=torch.float32, device=dev)
+                val[:m] = self._nn_val[keep]
+                self._nn_val = val
+            self._nn_rows = m
+        else:
+            self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0  # (the lists hold the old row numbers: dropped, not kept as a trap)
         if m == 0:
             self._has_pids = None
         return new_of
@@ -569,7 +613,9 @@ class GalleryIndex:
         number); -1 in every slot of a removed row.  1 <= n <= 8, n <= live_count.  ceil(len / 32) passes of the one-pass kernel
         (the masked form with the cached tombstone words once rows were removed), panels of 32 consecutive gallery rows as the
         query panel - in place in the P16 storage, the ragged last one through the cached zero-padded panel - so the similarities
-        are bit-identical to the dense trid_gemm_p16 product of the index's own operands.  Quadratic in len; no host read."""
+        are bit-identical to the dense trid_gemm_p16 product of the index's own operands.  The kernel's values are kept beside the
+        lists (``neighbour_values``, -inf in every slot of a removed row): refresh_neighbours merges by them.  Quadratic in len; no
+        host read."""
         if n < 1 or n > MAX_NEIGHBOURS:
             raise ValueError("GalleryIndex.build_neighbours: n must be in [1, %d]; got %d" % (MAX_NEIGHBOURS, n))
         G = self._n
@@ -577,37 +623,133 @@ class GalleryIndex:
             raise ValueError("GalleryIndex.build_neighbours: the index is empty")
         if n > self.live_count:
             raise ValueError("GalleryIndex.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
-        L = ops.L.load()
-        tail = G % SMALL_Q
-        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, SMALL_Q, n, 0),
-                   L.trid_index_search_ws_bytes(G, tail, n, 0) if tail else 0)
-        q16, _, _, lists = self._workspace(need)
-        words = self._mask_words(None) if self._dead else None
         dev = self._rows.device
-        vals = torch.empty(SMALL_Q, n, dtype=torch.float32, device=dev)
-        found = torch.empty(G, n, dtype=torch.int64, device=dev)
-        for at in range(0, G, SMALL_Q):
-            Q = min(SMALL_Q, G - at)
+        found, vals = self._neighbour_panels(0, G, n)
+        if self._nn is None or self._nn.shape[1] != n or self._nn.shape[0] < self.capacity:
+            self._nn = torch.empty(self.capacity, n, dtype=torch.int32, device=dev)
+        if self._nn_val is None or self._nn_val.shape != self._nn.shape:
+            self._nn_val = torch.empty(self.capacity, n, dtype=torch.float32, device=dev)
+        self._nn[:G].copy_(found)
+        self._nn[G:] = -1
+        self._nn_val[:G].copy_(vals)
+        self._nn_val[G:] = float("-inf")
+        if self._dead:
+            self._nn[:G].masked_fill_(~self._live[:G, None], -1)
+            self._nn_val[:G].masked_fill_(~self._live[:G, None], float("-inf"))
+        self._nn_ok, self._nn_rows = True, G
+
+    def _neighbour_search(self, panel, Q, n, words, lists, vals, found):
+        """one pass of the one-pass kernel with k = n: the Q rows of ``panel`` as the queries against the whole P16 gallery"""
+        G = self._n
+        if words is None:
+            call("trid_index_search_p16", _p(panel), _p(self._p16), _p(self._unit), Q, G, n, 0, _p(vals), _p(found), _p(lists), 0, stream())
+        else:
+            call("trid_index_search_masked_p16", _p(panel), _p(self._p16), _p(self._unit), _p(words), Q, G, n, 0, _p(vals), _p(found), _p(lists), 0, stream())
+
+    def _neighbour_workspace(self, n):
+        """-> (the cached zero-padded panel, the kernel's list workspace, the tombstone words or None) for neighbour searches at k = n
+        with any number of panel rows"""
+        L = ops.L.load()
+        need = max(L.trid_index_search_ws_bytes(self._n, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(self._n, SMALL_Q, n, 0))
+        q16, _, _, lists = self._workspace(need)  # (workers x Q x k x 8 bytes: the full panel covers every smaller one)
+        return q16, lists, (self._mask_words(None) if self._dead else None)
+
+    def _fill_panel(self, q16, src, Q):
+        """the Q P16 rows ``src`` into the cached zero-padded panel (bit copies: they carry the fixed unit scale)"""
+        q16.view(torch.int32)[:Q].copy_(src.view(torch.int32))
+        if Q < self._panel_rows:
+            q16[Q : self._panel_rows].zero_()
+        self._panel_rows = Q
+
+    def _neighbour_panels(self, first, last, n):
+        """the panel loop of build_neighbours over the rows [first, last) -> (found int64 [last - first, n], vals fp32 [same]): panels
+        of 32 consecutive gallery rows as the query panel of the one-pass kernel with k = n against the WHOLE gallery (the masked form
+        once rows were removed) - full panels in place in the P16 storage, the ragged last one through the cached zero-padded panel.
+        Rows and values of removed rows are whatever the search gives: the caller overwrites them."""
+        q16, lists, words = self._neighbour_workspace(n)
+        dev = self._rows.device
+        vals = torch.empty(last - first, n, dtype=torch.float32, device=dev)
+        found = torch.empty(last - first, n, dtype=torch.int64, device=dev)
+        for at in range(first, last, SMALL_Q):
+            Q = min(SMALL_Q, last - at)
             if Q == SMALL_Q:  # (the stored rows ARE a panel: packed with the unit scalar, 1024 bytes per row, 16-byte aligned)
                 panel = self._p16[at : at + SMALL_Q]
             else:
-                q16.view(torch.int32)[:Q].copy_(self._p16.view(torch.int32)[at : at + Q])
-                if Q < self._panel_rows:
-                    q16[Q : self._panel_rows].zero_()
-                self._panel_rows = Q
+                self._fill_panel(q16, self._p16[at : at + Q], Q)
                 panel = q16
-            if words is None:
-                call("trid_index_search_p16", _p(panel), _p(self._p16), _p(self._unit), Q, G, n, 0, _p(vals), _p(found[at:]), _p(lists), 0, stream())
-            else:
-                call("trid_index_search_masked_p16", _p(panel), _p(self._p16), _p(self._unit), _p(words), Q, G, n, 0, _p(vals), _p(found[at:]),
-                     _p(lists), 0, stream())
-        if self._nn is None or self._nn.shape[1] != n or self._nn.shape[0] < self.capacity:
-            self._nn = torch.empty(self.capacity, n, dtype=torch.int32, device=dev)
-        self._nn[:G].copy_(found)
-        self._nn[G:] = -1
-        if self._dead:
-            self._nn[:G].masked_fill_(~self._live[:G, None], -1)
-        self._nn_ok = True
+            self._neighbour_search(panel, Q, n, words, lists, vals[at - first :], found[at - first :])
+        return found, vals
+
+    def _candidate_scores(self, at, m, n0):
+        """-> the cached score buffer holding, as a row-major [m, n0] matrix at its start, the similarity of every old row i < n0 AS THE
+        QUERY to the m <= 32 rows from ``at``: trid_gemm_p16 with the m P16 rows as A (gallery role) and the P16 rows [0, n0) as B
+        (query role), both at the unit scale - the operand roles of the build's products, so the same fp32 numbers (DESIGN.md section
+        7j).  Always the tile kernel: the streaming short-K kernel ops.gemm_p16 would pick for n0 % 32 == 0 sums in another order."""
+        cand = self._score_buffer(self._ws.get("cols", SMALL_Q))  # (capacity * cols >= 32 * n0 floats)
+        ops.gemm_p16(ops.P16(self._p16[at : at + m], self._unit), ops.P16(self._p16[:n0], self._unit), cand, m, n0, self.dim, n0, tile_only=True)
+        return cand
+
+    def refresh_neighbours(self):
+        """Bring a stale neighbour graph up to date EXACTLY, without the quadratic rebuild -> (new_rows, redone_rows): the live rows
+        appended since the graph was last current, and the older rows whose lists had to be recomputed because they held a row that
+        was removed since.  Lists and values afterwards equal those of build_neighbours(n) on the same contents bit for bit.
+        Needs ``neighbours_refreshable`` (RuntimeError naming build_neighbours otherwise: never built, dropped by compact, loaded
+        without values) and n <= live_count (the ValueError of build_neighbours); both are checked before anything is modified.  A
+        current graph returns (0, 0) without a launch.  With n0 rows covered and len rows now:
+          * per group of at most 32 new rows at ``at``: the product of the group's P16 rows (A, gallery role) with the P16 rows
+            [0, n0) (B, query role) at the unit scale on the tile kernel trid_gemm_p16 - the definition's direction: old row i as the
+            B panel - into the cached score buffer, then ONE trid_index_nn_merge_f32 with cand_first = at, rows = n0; removals
+            only: one merge launch with m = 0;
+          * the lists of the new rows [n0, len) from build_neighbours' own panel loop over that range;
+          * the merge flags every old live row whose list holds a removed row: the flags are read once on the host (refresh is not
+            the latency path, like add and remove), the flagged rows' P16 rows are gathered 32 at a time into the cached panel,
+            searched with k = n and scattered back.
+        Exact: a live old row whose list holds no removed row keeps it as its top n over the still-live old rows (removing
+        non-members cannot change a top n), and merging the live new rows into it gives the top n over all live rows; every other row
+        is recomputed from scratch.  A recorded search must be recorded again afterwards, as after a build."""
+        if not self.neighbours_refreshable:
+            raise RuntimeError("GalleryIndex.refresh_neighbours: %s; call build_neighbours() first" % (
+                "there is no neighbour graph" if self._nn is None else "the neighbour graph was loaded without its values"))
+        n = self._nn.shape[1]
+        if n > self.live_count:
+            raise ValueError("GalleryIndex.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
+        if self._nn_ok:
+            return 0, 0
+        n0, n1 = self._nn_rows, self._n
+        dev = self._rows.device
+        redo = torch.zeros(n0, dtype=torch.uint8, device=dev)
+        live = self._live  # (bool storage: one byte per row, 0 / 1)
+
+        def merge(cand, m, at):
+            call("trid_index_nn_merge_f32", _p(cand), n0, m, at, n0, _p(live), _p(self._nn), _p(self._nn_val), n, _p(redo), stream())
+
+        if n1 == n0:
+            merge(None, 0, n0)
+        else:
+            for at in range(n0, n1, SMALL_Q):
+                m = min(SMALL_Q, n1 - at)
+                merge(self._candidate_scores(at, m, n0), m, at)
+            found, vals = self._neighbour_panels(n0, n1, n)
+            self._nn[n0:n1].copy_(found)
+            self._nn_val[n0:n1].copy_(vals)
+            dead = ~self._live[n0:n1, None]
+            self._nn[n0:n1].masked_fill_(dead, -1)
+            self._nn_val[n0:n1].masked_fill_(dead, float("-inf"))
+        again = torch.nonzero(redo).reshape(-1)  # (the one host read: how many rows, and which)
+        if again.numel():
+            q16, lists, words = self._neighbour_workspace(n)
+            vals = torch.empty(SMALL_Q, n, dtype=torch.float32, device=dev)
+            found = torch.empty(SMALL_Q, n, dtype=torch.int64, device=dev)
+            for at in range(0, again.numel(), SMALL_Q):
+                rows = again[at : at + SMALL_Q]
+                Q = rows.numel()
+                self._fill_panel(q16, self._p16.view(torch.int32)[rows], Q)
+                self._neighbour_search(q16, Q, n, words, lists, vals, found)
+                self._nn[rows] = found[:Q].int()
+                self._nn_val[rows] = vals[:Q]
+        new_rows = int(self._live[n0:n1].sum()) if n1 > n0 else 0
+        self._nn_ok, self._nn_rows = True, n1
+        return new_rows, int(again.numel())
 
     def search_reranked(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
         """-> (values [Q,k] f32, rows [Q,k] i64): the exact k best allowed rows of every query by RE-RANKED score, similarity +
@@ -645,11 +787,14 @@ class GalleryIndex:
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
         """the normalised fp32 rows, the pids (None without) and the liveness (bool [len]; None when nothing was removed); P16 is
-        re-derived on load; "neighbours": the int32 [len, n] lists of a CURRENT neighbour graph, None otherwise"""
+        re-derived on load; "neighbours": the int32 [len, n] lists of a CURRENT neighbour graph, None otherwise; "neighbour_values":
+        their fp32 [len, n] values when the graph is current and holds them, None otherwise"""
+        current = self.neighbours_current and self._n != 0
         return {"rows": None if self._rows is None else self._rows[: self._n].clone(),
                 "pids": None if not self._has_pids else self._pids[: self._n].clone(),
                 "live": None if not self._dead else self._live[: self._n].clone(),
-                "neighbours": None if not self.neighbours_current or self._n == 0 else self._nn[: self._n].clone()}
+                "neighbours": self._nn[: self._n].clone() if current else None,
+                "neighbour_values": self._nn_val[: self._n].clone() if current and self.neighbours_refreshable else None}
 
     @staticmethod
     def _check_neighbours(nn, rows):
@@ -664,24 +809,34 @@ class GalleryIndex:
     def load_state_dict(self, sd):
         """Replace the contents.  The rows are taken as they are (already normalised: no second normalisation) and re-packed.  A
         state dict without "live" (as written before removal existed) loads as all-live.  "neighbours" present and not None: the
-        lists are adopted as the current neighbour graph; a dict without them loads with no graph."""
+        lists are adopted as the current neighbour graph; a dict without them loads with no graph.  "neighbour_values" (fp32, shaped
+        like the lists; ValueError otherwise, and when "neighbours" is None) is adopted with them: the graph is then refreshable; lists
+        without values load as a current graph that refresh_neighbours refuses.  A dict with no "neighbours" key at all loads with
+        no graph whatever else it holds, as it always did."""
         rows = sd["rows"]
         if rows is None or rows.shape[0] == 0:
             self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
-            self._nn, self._nn_ok = None, False
+            self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0
             return
         if rows.shape[0] > MAX_ROWS:
             raise ValueError("GalleryIndex.load_state_dict: at most %d rows; got %d" % (MAX_ROWS, rows.shape[0]))
         nn = sd.get("neighbours")
         if nn is not None:
             self._check_neighbours(nn, rows.shape[0])
+        val = sd.get("neighbour_values") if "neighbours" in sd else None  # (no "neighbours" key at all: no graph, as before the values existed)
+        if val is not None:
+            if nn is None:
+                raise ValueError("GalleryIndex.load_state_dict: neighbour_values without neighbours")
+            if not torch.is_tensor(val) or val.dtype != torch.float32 or tuple(val.shape) != tuple(nn.shape):
+                raise ValueError("GalleryIndex.load_state_dict: neighbour_values must be a float32 %s tensor like neighbours; got %s" % (
+                    list(nn.shape), "%s %s" % (val.dtype, list(val.shape)) if torch.is_tensor(val) else type(val)))
         x = self._check_rows("load_state_dict", rows)
         n = x.shape[0]
         live = sd.get("live")
         if live is not None and (not torch.is_tensor(live) or live.numel() != n):
             raise ValueError("GalleryIndex.load_state_dict: live must hold one entry per row (%d)" % n)
         self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
-        self._nn, self._nn_ok = None, False
+        self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0
         self._reserve(n, x.device)
         self._rows[:n].copy_(x)
         self._pack_into(0, n)
@@ -697,4 +852,7 @@ class GalleryIndex:
         if nn is not None:
             self._nn = torch.full((self.capacity, nn.shape[1]), -1, dtype=torch.int32, device=x.device)
             self._nn[:n].copy_(nn.to(x.device))
-            self._nn_ok = True
+            self._nn_ok, self._nn_rows = True, n
+            if val is not None:
+                self._nn_val = torch.full((self.capacity, nn.shape[1]), float("-inf"), dtype=torch.float32, device=x.device)
+                self._nn_val[:n].copy_(val.to(x.device))

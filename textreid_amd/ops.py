@@ -327,12 +327,14 @@ def bn_bwd_fusable(y, M, N, fmt=1):
 
 
 def gemm_p16(A, B, C, M, N, K, ldc, conv=None, alpha=1.0, accumulate=False, bias=None, stats=None, residual=None, ldres=0,
-             relu=False, splits=1, strideSplit=0, variant=None, minmax=False, cmask=None, bn_bwd=None):
+             relu=False, splits=1, strideSplit=0, variant=None, minmax=False, cmask=None, bn_bwd=None, tile_only=False):
     """C[M,N] = alpha * A . B^T with both operands P16: A [M][K] (or an NHWC image [B,H,W,Cin] with conv=(H,W,Cin),
     K = 9*Cin), B [N][K].  minmax: the BatchNorm partials `stats` are [tiles][N][4] = (mean, M2, min, max).
     cmask (with accumulate, ldc == N): a relu_mask of bn_apply_p16 over C; C = A . B^T + (bit ? C : 0).
-    bn_bwd: a BnBwdSums - C is a gradient that feeds that BatchNorm layer's backward; its sums come out of the epilogue."""
-    if (USE_STREAM and conv is None and A.fmt == 1 and B.fmt == 1 and C.dtype == torch.float32 and stats is None and alpha == 1.0
+    bn_bwd: a BnBwdSums - C is a gradient that feeds that BatchNorm layer's backward; its sums come out of the epilogue.
+    tile_only: always the tile kernel trid_gemm_p16, never the streaming short-K kernel (whose sums agree with it to the last bits
+    only): for callers that compare the product bit for bit with other trid_gemm_p16 products (GalleryIndex.refresh_neighbours)."""
+    if (USE_STREAM and not tile_only and conv is None and A.fmt == 1 and B.fmt == 1 and C.dtype == torch.float32 and stats is None and alpha == 1.0
             and bias is None and residual is None and not relu and splits == 1 and bn_bwd is None and gemm_p16_stream_rows(M, N, K, accumulate)
             and (cmask is None or N % 256 == 0)):
         return gemm_p16_stream(A, B, C, M, N, K, ldc, accumulate=accumulate, cmask=cmask)  # short-K data gradients (conv1 of a block)

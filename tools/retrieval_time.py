@@ -26,7 +26,14 @@ with an event pair around every library call (the dense product, the deep select
 --rerank K [K ...]: GalleryIndex.build_neighbours(5) timed once (build_neighbours_ms), then search_reranked(k=K) and shortlist(k=K) of the
 same index for each K, timed in the same process alternating with the others.  Each Q entry gains reranked_ms and reranked_shortlist_ms
 {K: median, min, max}, reranked_over_shortlist {K: ratio of the medians}, reranked_split_ms {K: {entry point: ms}} (the bonus pass is
-trid_index_rerank_add_f32) and bonus_floor_ms: the graph's G * n * 4 bytes read once per panel of 32 queries, at 6.3 TB/s."""
+trid_index_rerank_add_f32) and bonus_floor_ms: the graph's G * n * 4 bytes read once per panel of 32 queries, at 6.3 TB/s.
+--refresh M [M ...]: after the Q loop and a timed build_neighbours(5) (the one of --rerank if given), per M: M rows are appended and
+GalleryIndex.refresh_neighbours() is timed (add_refresh_ms, add_counts = what it returned), then M random live rows are removed and it is
+timed again (remove_refresh_ms, remove_counts) - each one call after one untimed warm-up refresh of either kind; each change is then made
+a second time with an event pair around every library call of the refresh (add_split_ms / remove_split_ms per entry point).  Next to them
+build_over_add_refresh / build_over_remove_refresh (build_neighbours_ms over each) and add_floor_ms: the bytes a refresh after the add
+needs (per group of 32 new rows: the old P16 rows for the product and the gallery for the search pass, the candidate buffer written and
+read, lists and values read and written) at 6.3 TB/s."""
 import json, os, sys, time
 import torch
 
@@ -63,6 +70,14 @@ def index_main(argv):
             rerank.append(int(argv[j]))
             j += 1
         argv = argv[:i] + argv[j:]
+    refresh = []
+    if "--refresh" in argv:  # (as --deep: every bare number after it is an M)
+        i = argv.index("--refresh")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            refresh.append(int(argv[j]))
+            j += 1
+        argv = argv[:i] + argv[j:]
     masked = None
     if "--masked" in argv:
         i = argv.index("--masked")
@@ -75,7 +90,7 @@ def index_main(argv):
     CALLS, WARM, K, HBM = 20, 3, 10, 6.3e12
     gen = torch.Generator(device="cpu").manual_seed(7)
     g_raw = (torch.randn(G, 256, generator=gen) * 3.0).cuda()
-    idx = GalleryIndex(capacity=G)
+    idx = GalleryIndex(capacity=G + 2 * sum(refresh) + (1 if refresh else 0))  # (--refresh appends 2 M rows per M: no growth inside the measurement)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     idx.add(g_raw)
@@ -197,6 +212,55 @@ def index_main(argv):
         ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
         ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
         line["Q"][str(Q)] = ent
+    if refresh:  # last: it changes the index (rows appended, rows removed)
+        from textreid_amd import lib as LIB
+
+        if "build_neighbours_ms" not in line:
+            line["build_neighbours_ms"], line["neighbours_n"], line["build_panels"] = timed(lambda: idx.build_neighbours(5)), 5, (G + 31) // 32
+        n = line["neighbours_n"]
+
+        def one_refresh(change):
+            """change() makes the graph stale -> (wall ms of refresh_neighbours, its counts); then the same change again with an event
+            pair around every library call of the refresh, summed per entry point"""
+            change()
+            counts = []
+            ms = timed(lambda: counts.append(idx.refresh_neighbours()))
+            change()
+            torch.cuda.synchronize()
+            LIB.TRACE = []
+            idx.refresh_neighbours()
+            torch.cuda.synchronize()
+            trace, LIB.TRACE = LIB.TRACE, None
+            split = {}
+            for name, _, e0, e1 in trace:
+                split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
+            return ms, list(counts[0]), split
+
+        idx.add((torch.randn(1, 256, generator=gen) * 3.0).cuda())  # warm-up: every kernel of a refresh has run once
+        idx.refresh_neighbours()
+        idx.remove(rows=[0])
+        idx.refresh_neighbours()
+        line["refresh"] = {}
+        for M in refresh:
+            def add_rows():
+                idx.add((torch.randn(M, 256, generator=gen) * 3.0).cuda())
+
+            def remove_rows():
+                live = torch.nonzero(idx.live).reshape(-1)
+                idx.remove(rows=live[torch.randperm(live.numel(), generator=gen)[:M].to(live.device)])
+
+            rows_before = len(idx)
+            a_ms, a_counts, a_split = one_refresh(add_rows)
+            r_ms, r_counts, r_split = one_refresh(remove_rows)
+            groups = (M + 31) // 32
+            # the bytes one refresh after an add needs: per group of 32 new rows the old P16 rows read by the product, the candidate
+            # buffer written and read once, the lists and values read and written, and one search pass over the P16 gallery
+            add_bytes = groups * (2 * rows_before * 1024 + 2 * min(M, 32) * rows_before * 4 + 2 * rows_before * n * 8)
+            line["refresh"][str(M)] = {"rows_before": rows_before, "add_refresh_ms": a_ms, "add_counts": a_counts, "add_split_ms": a_split,
+                                       "add_bytes": add_bytes, "add_floor_ms": add_bytes / HBM * 1e3,
+                                       "remove_refresh_ms": r_ms, "remove_counts": r_counts, "remove_split_ms": r_split,
+                                       "build_over_add_refresh": line["build_neighbours_ms"] / a_ms,
+                                       "build_over_remove_refresh": line["build_neighbours_ms"] / r_ms}
     print(json.dumps(line), flush=True)
 
 
