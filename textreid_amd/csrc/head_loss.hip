@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void infonce_partial_kernel(const float* __res
     if (vec) {
         for (int k = k0 + 4 * threadIdx.x; k < k1; k += 1024) {
             const float4 v = *reinterpret_cast<const float4*>(r + k);
-            const uchar4 h = *reinterpret_cast<const uchar4*>(hit + k);  // k % 4 == 0; tail handled below
             if (k + 3 < k1) {
+                const uchar4 h = *reinterpret_cast<const uchar4*>(hit + k);  // k % 4 == 0; the tail reads hit byte-wise
                 if (!h.x) m = fmaxf(m, v.x * invT);
                 if (!h.y) m = fmaxf(m, v.y * invT);
                 if (!h.z) m = fmaxf(m, v.z * invT);
@@ -117,8 +117,8 @@ __global__ __launch_bounds__(256) void infonce_partial_kernel(const float* __res
         if (vec) {
             for (int k = k0 + 4 * threadIdx.x; k < k1; k += 1024) {
                 const float4 v = *reinterpret_cast<const float4*>(r + k);
-                const uchar4 h = *reinterpret_cast<const uchar4*>(hit + k);
                 if (k + 3 < k1) {
+                    const uchar4 h = *reinterpret_cast<const uchar4*>(hit + k);
                     if (!h.x) l += expf(v.x * invT - m);
                     if (!h.y) l += expf(v.y * invT - m);
                     if (!h.z) l += expf(v.z * invT - m);

@@ -41,6 +41,16 @@ def _check(*ts):
             raise RuntimeError("textreid_amd losses run on the HIP kernel library only (CUDA tensors); no CPU fallback")
 
 
+def _pad_cols(x, Cp):
+    """x [rows, C] with its feature axis zero-padded to Cp columns (the GEMMs need a reduction length and leading dimensions
+    % 4: a feature size that is no multiple of 4 runs through padded copies, the zeros add nothing to any product)"""
+    if x.shape[1] == Cp:
+        return x
+    xp = torch.zeros(x.shape[0], Cp, device=x.device)
+    xp[:, : x.shape[1]].copy_(x)
+    return xp
+
+
 class _InstanceLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, projection, v, t, labels, epsilon, scale, norm):
@@ -54,15 +64,19 @@ class _InstanceLossFn(torch.autograd.Function):
         E2 = torch.cat([v.detach(), t.detach()], dim=0).contiguous()
         if norm:  # losses.py:45-47: the embeddings L2-normalised as well
             E2, inv_e = ops.l2norm_rows(E2)
-        logits = ops.linear(E2, pnt, alpha=float(scale))  # [2B, ldn] (losses.py:52-53: scale * embed @ normalize(projection))
+        Cp = (C + 3) // 4 * 4
+        E2g, pntg = _pad_cols(E2, Cp), _pad_cols(pnt, Cp)
+        logits = ops.linear(E2g, pntg, alpha=float(scale))  # [2B, ldn] (losses.py:52-53: scale * embed @ normalize(projection))
         labels2 = torch.cat([labels, labels]).long().contiguous()
         rows = ops.empty((2 * B,), v)
         call("trid_smooth_ce_rows_f32", _p(logits), _p(labels2), _p(rows), 2 * B, N, ldn, float(epsilon), 1.0 / B,
              stream())
         loss = ops.empty((1,), v)
         ops.sum_to(rows, loss, 1.0 / B)
-        dE2 = ops.matmul_nn(logits, pnt, alpha=float(scale))
-        dpnt = ops.matmul_tn(logits, E2, alpha=float(scale))
+        dE2 = ops.matmul_nn(logits, pntg, alpha=float(scale))
+        dpnt = ops.matmul_tn(logits, E2g, alpha=float(scale))
+        if Cp != C:
+            dE2, dpnt = dE2[:, :C].contiguous(), dpnt[:, :C].contiguous()
         if norm:
             dE2 = ops.l2norm_rows_bwd(dE2, E2, inv_e)
         dproj = ops.empty((C, N), v)
@@ -227,7 +241,9 @@ class _CmpcFn(torch.autograd.Function):
         dots = ops.empty((2 * B,), v)
         inv = ops.empty((2 * B,), v)
         call("trid_cross_project_rows_f32", _p(vd), _p(td), _p(X), _p(dots), _p(inv), B, C, stream())
-        logits = ops.linear(X, pnt)  # [2B, ldn]
+        Cp = (C + 3) // 4 * 4
+        Xg, pntg = _pad_cols(X, Cp), _pad_cols(pnt, Cp)
+        logits = ops.linear(Xg, pntg)  # [2B, ldn]
         labels2 = torch.cat([labels, labels]).long().contiguous()
         prec = None
         if verbose:  # the arg-max is taken before the CE kernel turns the logits into their gradient (:92-96)
@@ -240,8 +256,10 @@ class _CmpcFn(torch.autograd.Function):
         call("trid_smooth_ce_rows_f32", _p(logits), _p(labels2), _p(rows), 2 * B, N, ldn, 0.0, 1.0 / B, stream())
         loss = ops.empty((1,), v)
         ops.sum_to(rows, loss, 1.0 / B)
-        dX = ops.matmul_nn(logits, pnt)
-        dpnt = ops.matmul_tn(logits, X)
+        dX = ops.matmul_nn(logits, pntg)
+        dpnt = ops.matmul_tn(logits, Xg)
+        if Cp != C:
+            dX, dpnt = dX[:, :C].contiguous(), dpnt[:, :C].contiguous()
         dproj = ops.empty((C, N), v)
         call("trid_colnorm_bwd_f32", _p(dpnt), _p(pnt), _p(invn), _p(dproj), C, N, ldn, stream())
         dv, dt = torch.empty_like(vd), torch.empty_like(td)
