@@ -818,6 +818,34 @@ int trid_topk_rows_deep_chunk(int k);
 long long trid_topk_rows_deep_ws_bytes(int Q, int G, int k, int chunk);
 int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, int Q, int G, int k, const uint32_t* mask_words,
                             long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk, void* stream);
+/* The deep select over GIVEN pairs (csrc/topk_deep.hip; step 2 of GalleryIndex.shortlist_pids, evaluation.topk_distinct_rows): the
+ * select above where level 1 reads the pair (val[q * ld_q + s * ld_g], col[q * ld_q + s * ld_g]), int32 columns, for the slots
+ * 0 <= s < n_slots instead of numbering the columns itself.  A column of INT_MAX (0x7fffffff) is the sentinel WHATEVER its value: the
+ * slot is absent.  The other columns of a row are distinct (the caller's contract).  Order: value descending by float comparison,
+ * then the GIVEN column ascending (+0 == -0 tie by column, the original bits come back; a real -inf is an ordinary value).  out_idx =
+ * column + idx_offset, -1 for a sentinel; a row with fewer than k present slots ends in (-inf, -1).  There are no mask words: absent
+ * is the sentinel.  k in [1, 1024], k <= n_slots, Q * ceil(n_slots / chunk) < 2^24, aliasing strides refused, chunk, the workspace
+ * (trid_topk_rows_deep_ws_bytes(Q, n_slots, k, chunk)), the merge levels and the capture rule are those of trid_topk_rows_deep_f32;
+ * val / col 4-byte, out_idx / ws 8-byte aligned. */
+int trid_topk_rows_deep_pairs_f32(const float* val, const int32_t* col, long long ld_q, long long ld_g, int Q, int n_slots, int k,
+                                  long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk,
+                                  void* stream);
+/* Group best (csrc/index_group.hip; step 1 of GalleryIndex.shortlist_pids, evaluation.topk_distinct_rows): for every (group s, query
+ * q) of a score matrix addressed as in the deep select (element (q, g) = scores[q * ld_q + g * ld_g]; the [G, cols] product and
+ * row-major [Q, G] both work; aliasing strides are refused) the group's FIRST allowed row in the library's one order - value
+ * descending by float comparison, then row ascending; +0 == -0 tie by row and keep their bits; a real -inf is an ordinary value; NaN
+ * undefined.  The group table: order int32 [G] = the rows sorted by group, ascending row inside a group; starts int32 [n_groups + 1]
+ * = group s holds order[starts[s] .. starts[s + 1]).  mask_words: as in the deep select, NULL = every row allowed.  Outputs at
+ * [q * out_ld_q + s * out_ld_g] for 0 <= q < Q, 0 <= s < n_slots (aliasing strides refused): out_val fp32 the row's score bits,
+ * out_row int32 the row; (-inf, INT_MAX) when the group has no allowed row and in the padding slots n_groups <= s < n_slots.  "No
+ * allowed row" is told by the ROW: a group whose only allowed score is a real -inf is a result.  Device contents are not validated
+ * and cannot fault: an order entry outside [0, G) is skipped and never dereferenced, a starts pair is clamped to [0, G].  Q >= 1
+ * (groups of 32 queries on the grid's second dimension, at most 65535 of them), G >= 1, 0 <= n_groups <= n_slots, n_slots >= 1;
+ * every pointer 4-byte aligned.  One wave walks a group: a group of r rows is r / 2 dependent steps whatever the gallery holds
+ * beside it.  No host read, no allocation, one launch: it can be captured. */
+int trid_index_group_best_f32(const float* scores, long long ld_q, long long ld_g, int Q, int G, const int32_t* order,
+                              const int32_t* starts, int n_groups, int n_slots, const uint32_t* mask_words, float* out_val,
+                              int32_t* out_row, long long out_ld_q, long long out_ld_g, void* stream);
 /* The k-reciprocal bonus of GalleryIndex.search_reranked (csrc/index_rerank.hip), IN PLACE on a score matrix addressed as in the deep
  * select above (element (q, g) = scores[q * ld_q + g * ld_g], the [G, cols] product and row-major [Q, G] both work, aliasing strides
  * are refused), between the dense product and the select.  qnn [Q, n] int64: each query's own neighbour rows (the out_idx of a deep

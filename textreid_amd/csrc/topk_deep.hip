@@ -14,6 +14,9 @@
 //            sentinel (-inf, INT_MAX), which sorts behind every real pair (a real -inf has a lower column);
 //   merges : a workgroup loads chunk / k lists of the level before.  The number of levels depends on (G, k, chunk) only.
 // Order: value descending by float comparison (+0 == -0), then column ascending.  NaN: undefined.
+// "trid_topk_rows_deep_pairs_f32" is the same select with another level 1 (template parameter PAIRS): the column of every element is
+// GIVEN (int32, addressed like the values) instead of numbered, a given column of INT_MAX is the sentinel whatever its value, and
+// there are no mask words.  The merge levels are shared: they only ever saw (value, column) pairs.
 
 #include "common.h"
 
@@ -32,6 +35,7 @@ struct __attribute__((aligned(8))) DeepPair {
 struct DeepArgs {
     // level 1
     const float* sim;
+    const int* col;  // PAIRS: the given column of every element, addressed like sim (DEEP_SENTINEL = absent)
     long long ld_q, ld_g;
     const uint32_t* mask;
     int G, chunk;
@@ -106,7 +110,8 @@ struct DeepBlock {
 
 // RB = min(16, P / 256, K2), at least 2: every stage of distance < RB runs on blocks in registers - one LDS pass for all of them
 // instead of one pass and one barrier each.  K2 == 1 has no stages at all (RB = 2 is never used then).
-template <bool FIRST, int RB>
+// PAIRS (level 1 only): the columns are GIVEN (a.col, addressed like a.sim) instead of numbered - trid_topk_rows_deep_pairs_f32.
+template <bool FIRST, int RB, bool PAIRS = false>
 __global__ __launch_bounds__(256) void topk_deep_kernel(const DeepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int P = a.P, K2 = a.K2, k = a.k;
@@ -119,24 +124,32 @@ __global__ __launch_bounds__(256) void topk_deep_kernel(const DeepArgs a) {
     if (FIRST) {
         const long long g0 = (long long)w * a.chunk;
         const float* r = a.sim + (long long)q * a.ld_q;
+        const int* rc = PAIRS ? a.col + (long long)q * a.ld_q : nullptr;
         // eight independent loads in flight per thread: with ld_q == 1 every element is a 128-byte line of its own
         for (int i0 = tid; i0 < P; i0 += 8 * 256) {
             float x[8];
+            int c[8];
             bool ok[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = i0 + u * 256;
                 const long long g = g0 + i;
                 ok[u] = i < P && g < a.G;
-                if (ok[u] && a.mask != nullptr) ok[u] = (a.mask[g >> 5] >> (g & 31)) & 1u;
+                if (!PAIRS && ok[u] && a.mask != nullptr) ok[u] = (a.mask[g >> 5] >> (g & 31)) & 1u;
                 x[u] = ok[u] ? r[g * a.ld_g] : -INFINITY;
+                if (PAIRS) {  // a given column of DEEP_SENTINEL is absent whatever its value: it takes the sentinel's -inf
+                    c[u] = ok[u] ? rc[g * a.ld_g] : DEEP_SENTINEL;
+                    if (c[u] == DEEP_SENTINEL) x[u] = -INFINITY;
+                } else {
+                    c[u] = ok[u] ? (int)(g0 + i) : DEEP_SENTINEL;
+                }
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = i0 + u * 256;
                 if (i < P) {
                     sv[deep_at(i)] = x[u];
-                    si[deep_at(i)] = ok[u] ? (int)(g0 + i) : DEEP_SENTINEL;
+                    si[deep_at(i)] = c[u];
                 }
             }
         }
@@ -283,37 +296,39 @@ constexpr int DEEP_LDS_MAX = (DEEP_CHUNK_MAX + (DEEP_CHUNK_MAX >> 5)) * (int)siz
 // of EVERY instantiation, so that a later call - a recorded one, whose k may pick another instantiation than the eager call
 // before it - makes nothing but launches.  (The flags are written without synchronisation: two first calls at once both set the
 // same values.)
-static int deep_raise_lds() {
+static int deep_raise_lds(const char* who) {
     static bool raised[64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess && dev >= 0 && dev < 64 && raised[dev]) return TRID_OK;
     const void* fns[] = {(const void*)topk_deep_kernel<true, 2>,  (const void*)topk_deep_kernel<true, 4>,  (const void*)topk_deep_kernel<true, 8>,
                          (const void*)topk_deep_kernel<true, 16>, (const void*)topk_deep_kernel<false, 2>, (const void*)topk_deep_kernel<false, 4>,
-                         (const void*)topk_deep_kernel<false, 8>, (const void*)topk_deep_kernel<false, 16>};
+                         (const void*)topk_deep_kernel<false, 8>, (const void*)topk_deep_kernel<false, 16>,
+                         (const void*)topk_deep_kernel<true, 2, true>, (const void*)topk_deep_kernel<true, 4, true>,
+                         (const void*)topk_deep_kernel<true, 8, true>, (const void*)topk_deep_kernel<true, 16, true>};
     for (const void* fn : fns)
         if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, DEEP_LDS_MAX);
-    if (e != hipSuccess) { set_error("trid_topk_rows_deep_f32: cannot reserve %d B of LDS: %s", DEEP_LDS_MAX, hipGetErrorString(e)); return (int)e; }
+    if (e != hipSuccess) { set_error("%s: cannot reserve %d B of LDS: %s", who, DEEP_LDS_MAX, hipGetErrorString(e)); return (int)e; }
     if (dev >= 0 && dev < 64) raised[dev] = true;
     return TRID_OK;
 }
 
-template <bool FIRST, int RB>
-static int deep_launch_rb(const DeepArgs& a, long long groups, hipStream_t stream) {
+template <bool FIRST, int RB, bool PAIRS>
+static int deep_launch_rb(const char* who, const DeepArgs& a, long long groups, hipStream_t stream) {
     const size_t lds = (size_t)(a.P + (a.P >> 5)) * sizeof(DeepPair);
-    hipLaunchKernelGGL((topk_deep_kernel<FIRST, RB>), dim3((unsigned)groups), dim3(256), lds, stream, a);
-    return check_launch("trid_topk_rows_deep_f32");
+    hipLaunchKernelGGL((topk_deep_kernel<FIRST, RB, PAIRS>), dim3((unsigned)groups), dim3(256), lds, stream, a);
+    return check_launch(who);
 }
 
-template <bool FIRST>
-static int deep_launch(const DeepArgs& a, long long groups, hipStream_t stream) {
+template <bool FIRST, bool PAIRS = false>
+static int deep_launch(const char* who, const DeepArgs& a, long long groups, hipStream_t stream) {
     int rb = a.P / 256 < a.K2 ? a.P / 256 : a.K2;  // pairs per register block: a thread's share of P, no longer than a run
     rb = rb > DEEP_RB_MAX ? DEEP_RB_MAX : rb < 2 ? 2 : rb;
     switch (rb) {
-        case 2: return deep_launch_rb<FIRST, 2>(a, groups, stream);
-        case 4: return deep_launch_rb<FIRST, 4>(a, groups, stream);
-        case 8: return deep_launch_rb<FIRST, 8>(a, groups, stream);
-        default: return deep_launch_rb<FIRST, 16>(a, groups, stream);
+        case 2: return deep_launch_rb<FIRST, 2, PAIRS>(who, a, groups, stream);
+        case 4: return deep_launch_rb<FIRST, 4, PAIRS>(who, a, groups, stream);
+        case 8: return deep_launch_rb<FIRST, 8, PAIRS>(who, a, groups, stream);
+        default: return deep_launch_rb<FIRST, 16, PAIRS>(who, a, groups, stream);
     }
 }
 
@@ -334,29 +349,32 @@ extern "C" long long trid_topk_rows_deep_ws_bytes(int Q, int G, int k, int chunk
     return (n1 + n2) * Q * k * (long long)sizeof(DeepPair);
 }
 
-extern "C" int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, int Q, int G, int k, const uint32_t* mask_words,
-                                       long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk,
-                                       void* stream_) {
-    TRID_REQUIRE(sim && out_val && out_idx && ws, "trid_topk_rows_deep_f32: null pointer");
-    TRID_REQUIRE(Q >= 1 && G >= 1, "trid_topk_rows_deep_f32: Q and G must be >= 1; got Q = %d, G = %d", Q, G);
-    TRID_REQUIRE(k >= 1 && k <= TOPK_DEEP_MAX && k <= G, "trid_topk_rows_deep_f32: k must be in [1,%d] and <= G = %d; got %d", TOPK_DEEP_MAX, G, k);
+// Both entries: the argument rules, level 1 (numbered columns with mask words, or the GIVEN columns `col`), then the merge levels.
+// who: the entry's name in every message; gname: what it calls its column count.
+static int deep_select(const char* who, const char* gname, const float* sim, const int32_t* col, bool pairs, long long ld_q, long long ld_g, int Q,
+                       int G, int k, const uint32_t* mask_words, long long idx_offset, float* out_val, int64_t* out_idx, void* ws,
+                       long long ws_bytes, int chunk, void* stream_) {
+    TRID_REQUIRE(sim && out_val && out_idx && ws && (col || !pairs), "%s: null pointer", who);
+    TRID_REQUIRE(Q >= 1 && G >= 1, "%s: Q and %s must be >= 1; got Q = %d, %s = %d", who, gname, Q, gname, G);
+    TRID_REQUIRE(k >= 1 && k <= TOPK_DEEP_MAX && k <= G, "%s: k must be in [1,%d] and <= %s = %d; got %d", who, TOPK_DEEP_MAX, gname, G, k);
     const int c = deep_chunk(k, chunk);
-    TRID_REQUIRE(c != 0, "trid_topk_rows_deep_f32: chunk must be 0 or a power of two in [max(64, 2 * next_pow2(k)) = %d, %d]; got %d",
+    TRID_REQUIRE(c != 0, "%s: chunk must be 0 or a power of two in [max(64, 2 * next_pow2(k)) = %d, %d]; got %d", who,
                  2 * next_pow2(k) > 64 ? 2 * next_pow2(k) : 64, DEEP_CHUNK_MAX, chunk);
     // two elements must not alias: one of the strides spans the whole extent of the other
     TRID_REQUIRE(ld_q >= 1 && ld_g >= 1 && (ld_q >= (long long)(G - 1) * ld_g + 1 || ld_g >= (long long)(Q - 1) * ld_q + 1),
-                 "trid_topk_rows_deep_f32: ld_q = %lld, ld_g = %lld make two elements of a [%d, %d] matrix alias", ld_q, ld_g, Q, G);
+                 "%s: ld_q = %lld, ld_g = %lld make two elements of a [%d, %d] matrix alias", who, ld_q, ld_g, Q, G);
     TRID_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sim) & 3u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(mask_words) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out_idx) & 7u) == 0,
-                 "trid_topk_rows_deep_f32: sim / mask_words must be 4-byte, out_idx / ws 8-byte aligned");
+                     (reinterpret_cast<uintptr_t>(mask_words) & 3u) == 0 && (reinterpret_cast<uintptr_t>(col) & 3u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(out_idx) & 7u) == 0,
+                 "%s: %s must be 4-byte, out_idx / ws 8-byte aligned", who, pairs ? "val / col" : "sim / mask_words");
     long long n1, n2;
     deep_lists(G, k, c, &n1, &n2);
-    TRID_REQUIRE(n1 * Q <= DEEP_GROUPS_MAX, "trid_topk_rows_deep_f32: Q * ceil(G / chunk) = %lld workgroups exceed the grid of %lld (2^32 threads)", n1 * Q,
+    TRID_REQUIRE(n1 * Q <= DEEP_GROUPS_MAX, "%s: Q * ceil(%s / chunk) = %lld workgroups exceed the grid of %lld (2^32 threads)", who, gname, n1 * Q,
                  DEEP_GROUPS_MAX);
     const long long need = trid_topk_rows_deep_ws_bytes(Q, G, k, chunk);
-    TRID_REQUIRE(ws_bytes >= need, "trid_topk_rows_deep_f32: ws_bytes = %lld, trid_topk_rows_deep_ws_bytes asks for %lld", ws_bytes, need);
+    TRID_REQUIRE(ws_bytes >= need, "%s: ws_bytes = %lld, trid_topk_rows_deep_ws_bytes asks for %lld", who, ws_bytes, need);
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = deep_raise_lds();
+    int rc = deep_raise_lds(who);
     if (rc) return rc;
 
     DeepPair* buf[2] = {reinterpret_cast<DeepPair*>(ws), reinterpret_cast<DeepPair*>(ws) + n1 * Q * k};
@@ -364,11 +382,11 @@ extern "C" int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long lo
     memset(&a, 0, sizeof(a));
     a.Q = Q; a.k = k; a.K2 = next_pow2(k);
     a.out_val = out_val; a.out_idx = (long long*)out_idx; a.idx_offset = idx_offset;
-    a.sim = sim; a.ld_q = ld_q; a.ld_g = ld_g; a.mask = mask_words; a.G = G; a.chunk = c;
+    a.sim = sim; a.col = (const int*)col; a.ld_q = ld_q; a.ld_g = ld_g; a.mask = mask_words; a.G = G; a.chunk = c;
     a.P = G < c ? (next_pow2(G) > 64 ? next_pow2(G) : 64) : c;  // (one short chunk: no more pairs than the row has; >= K2 as k <= G)
     a.nout = (int)n1;
     a.out = n1 > 1 ? buf[0] : nullptr;
-    rc = deep_launch<true>(a, n1 * Q, stream);
+    rc = pairs ? deep_launch<true, true>(who, a, n1 * Q, stream) : deep_launch<true>(who, a, n1 * Q, stream);
     if (rc) return rc;
     const int fan = c / k;
     int src = 0;
@@ -377,9 +395,23 @@ extern "C" int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long lo
         a.in = buf[src]; a.nin = (int)nin; a.fan = fan; a.nout = (int)nout;
         a.out = nout > 1 ? buf[src ^ 1] : nullptr;
         a.P = next_pow2((nin < fan ? nin : fan) * k);  // (>= 2 K2: at least two lists of k)
-        rc = deep_launch<false>(a, nout * Q, stream);
+        rc = deep_launch<false>(who, a, nout * Q, stream);
         if (rc) return rc;
         nin = nout;
     }
     return TRID_OK;
+}
+
+extern "C" int trid_topk_rows_deep_f32(const float* sim, long long ld_q, long long ld_g, int Q, int G, int k, const uint32_t* mask_words,
+                                       long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk,
+                                       void* stream_) {
+    return deep_select("trid_topk_rows_deep_f32", "G", sim, nullptr, false, ld_q, ld_g, Q, G, k, mask_words, idx_offset, out_val, out_idx, ws,
+                       ws_bytes, chunk, stream_);
+}
+
+extern "C" int trid_topk_rows_deep_pairs_f32(const float* val, const int32_t* col, long long ld_q, long long ld_g, int Q, int n_slots, int k,
+                                             long long idx_offset, float* out_val, int64_t* out_idx, void* ws, long long ws_bytes, int chunk,
+                                             void* stream_) {
+    return deep_select("trid_topk_rows_deep_pairs_f32", "n_slots", val, col, true, ld_q, ld_g, Q, n_slots, k, nullptr, idx_offset, out_val, out_idx,
+                       ws, ws_bytes, chunk, stream_);
 }

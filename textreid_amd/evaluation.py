@@ -87,6 +87,58 @@ def topk_rows(sim, k, mask=None):
     return vals, cols
 
 
+def topk_distinct_rows(sim, groups, k, mask=None):
+    """-> (values [Q,k] f32, rows [Q,k] i64): the k best DISTINCT groups of every row of a CUDA fp32 [Q, G] matrix, each by its first
+    allowed column in the library's order (value descending, then column ascending), 1 <= k <= 1024 - the definition of
+    GalleryIndex.search_pids on a given matrix.  groups: an integer tensor [G] (equal = one group).  trid_index_group_best_f32 over
+    the table of ``index.group_table(groups)`` (one host read: the group count), then trid_topk_rows_deep_pairs_f32 over max(groups,
+    k) slots; a row with fewer than k allowed groups ends in (-inf, -1) slots.  The values are the input's bit patterns; the rows
+    need not be contiguous.  mask: bool / uint8 [G] on the same device, true = the column may be returned.  The table, the pair
+    buffers and the workspace are allocated per call, as topk_rows does."""
+    from .index import group_table
+
+    if not torch.is_tensor(sim) or sim.dim() != 2:
+        raise ValueError("textreid_amd.evaluation.topk_distinct_rows: expected a [Q, G] tensor")
+    if not sim.is_cuda:
+        raise RuntimeError("textreid_amd.evaluation.topk_distinct_rows runs on the HIP kernel library only (CUDA tensors); no CPU fallback")
+    Q, G = sim.shape
+    if Q < 1 or G < 1 or k < 1 or k > MAX_DEEP_TOPK:
+        raise ValueError("textreid_amd.evaluation.topk_distinct_rows: k must be in [1, %d], Q >= 1, G >= 1; got k = %d, Q = %d, G = %d" % (MAX_DEEP_TOPK, k, Q, G))
+    groups = torch.as_tensor(groups)
+    if groups.dim() != 1 or groups.shape[0] != G or groups.is_floating_point():
+        raise ValueError("textreid_amd.evaluation.topk_distinct_rows: groups must be an integer tensor of shape [G = %d]" % G)
+    if sim.dtype != torch.float32:
+        sim = sim.float()
+    ld_q, ld_g = (1 if Q == 1 else sim.stride(0)), (1 if G == 1 else sim.stride(1))
+    if not (ld_q >= 1 and ld_g >= 1 and (ld_q >= (G - 1) * ld_g + 1 or ld_g >= (Q - 1) * ld_q + 1)):
+        sim = sim.contiguous()  # (an expanded view: its elements alias)
+        ld_q, ld_g = G, 1
+    dev = sim.device
+    words = None
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or mask.shape[0] != G:
+            raise ValueError("textreid_amd.evaluation.topk_distinct_rows: mask must be a bool or uint8 tensor of shape [G = %d]" % G)
+        if mask.device != dev:
+            raise ValueError("textreid_amd.evaluation.topk_distinct_rows: sim is on %s; got a mask on %s" % (dev, mask.device))
+        m = mask.contiguous()
+        words = torch.empty((G + 31) // 32, dtype=torch.int32, device=dev)
+        call("trid_index_pack_mask_u32", None, _p(m), G, _p(words), words.numel(), stream())
+    order, starts, n_groups = group_table(groups.to(dev))
+    n_slots = max(n_groups, k)
+    best_val = torch.empty(Q, n_slots, dtype=torch.float32, device=dev)
+    best_row = torch.empty(Q, n_slots, dtype=torch.int32, device=dev)
+    call("trid_index_group_best_f32", _p(sim), ld_q, ld_g, Q, G, _p(order), _p(starts), n_groups, n_slots, _p(words), _p(best_val), _p(best_row),
+         n_slots, 1, stream())
+    nws = ops.L.load().trid_topk_rows_deep_ws_bytes(Q, n_slots, k, 0)
+    if nws <= 0:
+        raise RuntimeError("trid_topk_rows_deep_pairs_f32: Q = %d, n_slots = %d, k = %d out of range" % (Q, n_slots, k))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    vals = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    rows = torch.empty(Q, k, dtype=torch.int64, device=dev)
+    call("trid_topk_rows_deep_pairs_f32", _p(best_val), _p(best_row), n_slots, 1, Q, n_slots, k, 0, _p(vals), _p(rows), _p(ws), nws, 0, stream())
+    return vals, rows
+
+
 def rank(similarity, q_pids, g_pids, topk=(1, 5, 10), get_mAP=True):
     """CMC (and mAP) of a given [Q, G] similarity matrix (evaluation.py:11-37).  get_mAP=False keeps max(topk) columns per query:
     up to 16 by trid_topk_rows_f32, up to 1024 by trid_topk_rows_deep_f32, beyond that a slice of the full argsort - one order

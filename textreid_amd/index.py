@@ -50,6 +50,18 @@ bit for bit - followed by ``trid_topk_rows_deep_f32`` (csrc/topk_deep.hip, DESIG
 score buffer of ``len * cols * 4`` bytes cached on the index and grown with it (cols = 32, or 64 if the tile kernel declines 32 columns:
 128 MB at 1e6 rows) plus the select workspace (``trid_topk_rows_deep_ws_bytes``: 3 MB at k = 100, 192 MB at k = 1024 for 1e6 rows).
 
+``shortlist_pids`` is the deep counterpart of ``search_pids``: the exact k best DISTINCT pids, k up to 1024, by the same definition (so
+``shortlist_pids(k <= 16)`` equals ``search_pids`` bit for bit, and with all pids different it equals ``shortlist``).  Over-fetching rows
+from ``shortlist`` and de-duplicating is not this: a person with many good images eats the list.  Two device steps after the dense
+product: ``trid_index_group_best_f32`` (csrc/index_group.hip) walks the cached group table (``group_table(pids)``:
+the rows sorted by pid and the start of every pid; derived state like the group ids, one host read of the group count when it is
+rebuilt after ``add`` / ``compact`` / ``load_state_dict``; ``remove`` leaves it valid) and leaves every pid's first allowed row per
+query, or the sentinel ``(-inf, INT_MAX)``, in a ``[n_slots, 32]`` pair of buffers; ``trid_topk_rows_deep_pairs_f32`` selects over
+those pairs, ties to the lower REPRESENTATIVE row.  ``n_slots = max(pids, k)``; a query with fewer than k allowed pids ends in
+``(-inf, -1, -1)`` slots and nothing is read back.  ``search_reranked_pids`` runs the same two steps on the bonus-modified buffer of
+``search_reranked``: a person's score is their best re-ranked row.  One wave walks a pid: a pid that holds most of the gallery is
+serial - the known limit.
+
 ``search_reranked`` is the second stage on the index itself: the exact top-k (k <= 1024) by the RE-RANKED score the evaluation's
 ``rerank=True`` tables measure, ``similarity + alpha * Jaccard(N(query), N(row))`` over neighbour lists of n rows (DESIGN.md section
 7i).  It needs the neighbour graph, derived state like the mask words and the group ids but built on request:
@@ -87,7 +99,7 @@ An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torc
 A recorded search answers against the gallery as it stood at the capture (row count, storage, tombstones and neighbour graph are
 part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours`` / ``refresh_neighbours``.
 
-Not built: ``search_pids`` beyond k = 16, gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
+Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
 or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
 pass); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).
@@ -127,6 +139,23 @@ def group_ids(pids):
     return out
 
 
+def group_table(pids):
+    """-> (order int32 [n], starts int32 [n_groups + 1], n_groups): the groups of ``group_ids(pids)`` as a table - group s holds the
+    rows ``order[starts[s] : starts[s + 1]]``, ascending (the same stable sort, the same numbering).  One host read, the group
+    count: like add, not the latency path."""
+    p = torch.as_tensor(pids).reshape(-1).long()
+    n = p.numel()
+    if n == 0:
+        return torch.empty(0, dtype=torch.int32, device=p.device), torch.zeros(1, dtype=torch.int32, device=p.device), 0
+    ordered, perm = torch.sort(p, stable=True)
+    step = torch.zeros(n, dtype=torch.int32, device=p.device)
+    step[1:] = ordered[1:] != ordered[:-1]
+    gid = torch.cumsum(step, 0, dtype=torch.int32)  # (of the sorted rows: ascending)
+    n_groups = int(gid[-1]) + 1
+    starts = torch.searchsorted(gid, torch.arange(n_groups + 1, dtype=torch.int32, device=p.device)).int()
+    return perm.int(), starts, n_groups
+
+
 class GalleryIndex:
     """``idx = GalleryIndex(); idx.add(image_embed, pids); vals, rows = idx.search(text_embed, k=10)``.  See the module docstring
     for the storage, the order rule, the one-stream rule and what is out of scope."""
@@ -146,6 +175,7 @@ class GalleryIndex:
         self._dead = 0      # removed rows among the first len (host count)
         self._words_ok = False  # the cached mask words of the tombstones are current
         self._gids_ok = False   # the cached group ids of the pids are current
+        self._gtab_ok = False   # the cached group table of the pids (order, starts, count) is current
         self._nn = None     # int32 [capacity, n]: the neighbour graph (build_neighbours), -1 in every slot of a removed row
         self._nn_ok = False     # the graph is current: no add / remove / compact since it was built or loaded
         self._nn_val = None  # fp32 [capacity, n]: the similarity of every list entry (refresh_neighbours merges by them), -inf in every slot of a removed row
@@ -235,7 +265,7 @@ class GalleryIndex:
             pids[: self._n].copy_(self._pids[: self._n])
             live[: self._n].copy_(self._live[: self._n])
         self._rows, self._p16, self._pids, self._live = rows, p16, pids, live
-        self._words_ok = self._gids_ok = False
+        self._words_ok = self._gids_ok = self._gtab_ok = False
         if self._nn is not None:  # (the lists grow with the storage like the other workspaces; growth alone changes nothing in them)
             nn = torch.full((new_cap, self._nn.shape[1]), -1, dtype=torch.int32, device=device)
             nn[: self._n].copy_(self._nn[: self._n])
@@ -293,7 +323,7 @@ class GalleryIndex:
         self._has_pids = has
         self._live[first : first + n] = True
         self._n = first + n
-        self._words_ok = self._gids_ok = False
+        self._words_ok = self._gids_ok = self._gtab_ok = False
         if self._nn is not None:  # (no list knows the new rows and they have none: the graph is stale until the next build or refresh)
             self._nn[first : first + n] = -1
             if self._nn_val is not None:
@@ -360,7 +390,7 @@ class GalleryIndex:
         pids[:m] = self._pids[keep]
         self._rows, self._p16, self._pids = rows, p16, pids
         self._live = torch.ones(cap, dtype=torch.bool, device=dev)
-        self._n, self._dead, self._words_ok, self._gids_ok = m, 0, False, False
+        self._n, self._dead, self._words_ok, self._gids_ok, self._gtab_ok = m, 0, False, False, False
         if keep_neighbours and self.neighbours_current and m:
             nn = torch.full((cap, self._nn.shape[1]), -1, dtype=torch.int32, device=dev)
             nn[:m] = new_of[self._nn[keep].long()].int()
@@ -464,7 +494,7 @@ class GalleryIndex:
             call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
 
     def _check_search(self, name, queries, k, mask, need_pids=False, max_k=MAX_K, need_graph=False):
-        """the argument rules search, search_pids, shortlist and search_reranked share, in the order the messages are promised -> the
+        """the argument rules search, search_pids, shortlist, shortlist_pids and the re-ranked searches share, in the order the messages are promised -> the
         queries, fp32 contiguous.  need_graph: a current neighbour graph, asked for after the argument rules and before the device's"""
         if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError("GalleryIndex.%s: expected a [Q, %d] tensor" % (name, self.dim))
@@ -572,10 +602,12 @@ class GalleryIndex:
         ops.gemm_p16(gallery, ops.P16(wide, self._unit), scores, G, cols, self.dim, cols)
         return scores
 
-    def _deep_workspace(self, *ks):
-        """the cached workspace of the deep select, large enough for a panel of 32 queries at every k given"""
+    def _deep_workspace(self, *ks, slots=None):
+        """the cached workspace of the deep select, large enough for a panel of 32 queries at every k given over the rows - and, with
+        ``slots`` = (n_slots, k), for the pairs select of k over n_slots group slots as well"""
         L = ops.L.load()
-        nws = max(L.trid_topk_rows_deep_ws_bytes(SMALL_Q, self._n, k, 0) for k in ks)
+        nws = max([L.trid_topk_rows_deep_ws_bytes(SMALL_Q, self._n, k, 0) for k in ks] +
+                  ([L.trid_topk_rows_deep_ws_bytes(SMALL_Q, slots[0], slots[1], 0)] if slots else []))
         ws = self._ws.get("deep")
         if ws is None or ws.numel() < nws:
             ws = torch.empty(nws, dtype=torch.uint8, device=self._rows.device)
@@ -605,6 +637,72 @@ class GalleryIndex:
             scores = self._dense_scores(q16)
             _deep_topk(_p(scores), 1, scores.shape[1], part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
         return vals, rows
+
+    # ------------------------------------------------------------------ deep distinct search
+    def _group_table(self):
+        """-> (order int32 [len], starts int32 [n_groups + 1], n_groups): the cached group table of the pids (``group_table``), derived
+        state like the group ids: rebuilt - one host read, the group count - on the first use after add / compact / load_state_dict
+        / growth, outside any capture like the workspace.  remove leaves it valid: a pid with no live row yields the sentinel."""
+        if not self._gtab_ok or "gtable" not in self._ws:
+            self._ws["gtable"] = group_table(self._pids[: self._n])
+            self._gtab_ok = True
+        return self._ws["gtable"]
+
+    def _group_best_buffers(self, n_slots):
+        """the cached best-pair buffers of one query panel, fp32 and int32 [n_slots, 32]: held for max(n_groups, MAX_SHORTLIST_K)
+        slots, so that a recording with another k than the eager call before it allocates nothing"""
+        held = max(n_slots, MAX_SHORTLIST_K)
+        val = self._ws.get("gbest_val")
+        if val is None or val.shape[0] < held:
+            val = torch.empty(held, SMALL_Q, dtype=torch.float32, device=self._rows.device)
+            self._ws["gbest_val"] = val
+            self._ws["gbest_row"] = torch.empty(held, SMALL_Q, dtype=torch.int32, device=self._rows.device)
+        return val, self._ws["gbest_row"]
+
+    def _distinct_setup(self, k):
+        """-> (table, n_slots, (best values, best rows)) of a distinct select of k: n_slots = max(n_groups, k), so that the select's
+        k <= n_slots holds without reading the number of allowed pids"""
+        table = self._group_table()
+        n_slots = max(table[2], k)
+        return table, n_slots, self._group_best_buffers(n_slots)
+
+    def _distinct_select(self, scores, Q, k, words, table, n_slots, best, ws, vals, rows):
+        """steps 1 and 2 on the score buffer of one panel: trid_index_group_best_f32 with the allow words into the best-pair buffers,
+        then trid_topk_rows_deep_pairs_f32 over the n_slots pairs of every query (ld_q = 1)"""
+        order, starts, n_groups = table
+        bv, br = best
+        call("trid_index_group_best_f32", _p(scores), 1, scores.shape[1], Q, self._n, _p(order), _p(starts), n_groups, n_slots, _p(words),
+             _p(bv), _p(br), 1, SMALL_Q, stream())
+        call("trid_topk_rows_deep_pairs_f32", _p(bv), _p(br), 1, SMALL_Q, Q, n_slots, k, 0, _p(vals), _p(rows), _p(ws), ws.numel(), 0, stream())
+
+    def shortlist_pids(self, queries, k=100, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64, pids [Q,k] i64): the exact k best DISTINCT pids of every query for 1 <= k <=
+        MAX_SHORTLIST_K = 1024, each by its best allowed row - the definition of search_pids (value descending, then row ascending,
+        inside a pid and between pids; pids = self.pids[rows]) at the depth of shortlist.  Per panel of 32 queries: the dense product
+        of shortlist into the cached score buffer; trid_index_group_best_f32 (csrc/index_group.hip) over the cached group table with
+        the allow words of ``live & mask`` - every pid's first allowed row, (-inf, INT_MAX) for a pid without one - into the cached
+        [n_slots, 32] best-pair buffers; trid_topk_rows_deep_pairs_f32 over those pairs, ordered by value and then by the
+        REPRESENTATIVE row.  n_slots = max(number of pids, k): the number of allowed pids is never read back, and a query with fewer
+        than k of them ends in (-inf, -1, -1) slots.  shortlist_pids(k <= 16) equals search_pids bit for bit.  queries, normalize,
+        mask: as search (no mask: k <= live_count).  The index must hold pids.  No host read; after one eager call (which builds the
+        group table - one read of the group count - the buffers and the workspaces) nothing is allocated but the outputs, so it can
+        be captured with torch.cuda.graph: a replay reads the queries' and the mask's contents at replay time; record again after
+        add / remove / compact.  One wave walks a pid's rows: a pid holding most of the gallery is serial."""
+        x = self._check_search("shortlist_pids", queries, k, mask, need_pids=True, max_k=MAX_SHORTLIST_K)
+        Q, G = x.shape[0], self._n
+        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
+        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        L = ops.L.load()
+        table, n_slots, best = self._distinct_setup(k)
+        ws = self._deep_workspace(slots=(n_slots, k))
+        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
+            part = x[at : at + SMALL_Q]
+            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
+            scores = self._dense_scores(q16)
+            self._distinct_select(scores, part.shape[0], k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
+        pids = self._pids[:G][rows].masked_fill_(rows < 0, -1)  # (a short slot's -1 indexes the last row: in range, then overwritten)
+        return vals, rows, pids
 
     # ------------------------------------------------------------------ neighbour graph and re-ranked search
     def build_neighbours(self, n=5):
@@ -762,14 +860,23 @@ class GalleryIndex:
         the result is exact, not a re-ordered shortlist.  alpha == 0.0 skips the bonus (and the select that only feeds it) and equals shortlist bit for bit.  queries,
         normalize, mask: as shortlist.  No host read; after one eager call nothing is allocated but the outputs and the queries'
         lists, so it can be captured with torch.cuda.graph; record again after add / remove / compact / build_neighbours."""
-        x = self._check_search("search_reranked", queries, k, mask, max_k=MAX_SHORTLIST_K, need_graph=True)
+        return self._reranked("search_reranked", queries, k, alpha, normalize, mask, distinct=False)
+
+    def _reranked(self, name, queries, k, alpha, normalize, mask, distinct):
+        """search_reranked (distinct=False) and search_reranked_pids (True) -> (values, rows): one panel loop, the product, the
+        query's own list and the bonus pass are shared; the final select is the deep row select or the two steps of shortlist_pids"""
+        x = self._check_search(name, queries, k, mask, need_pids=distinct, max_k=MAX_SHORTLIST_K, need_graph=True)
         alpha = float(alpha)
         Q, G, n = x.shape[0], self._n, self._nn.shape[1]
         vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
         rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
         words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
         L = ops.L.load()
-        ws = self._deep_workspace(k, n)
+        if distinct:
+            table, n_slots, best = self._distinct_setup(k)
+            ws = self._deep_workspace(n, slots=(n_slots, k))
+        else:
+            ws = self._deep_workspace(k, n)
         if alpha != 0.0:
             qnn = torch.empty(min(Q, SMALL_Q), n, dtype=torch.int64, device=x.device)
             qval = torch.empty(min(Q, SMALL_Q), n, dtype=torch.float32, device=x.device)
@@ -781,8 +888,22 @@ class GalleryIndex:
             if alpha != 0.0:
                 _deep_topk(_p(scores), 1, cols, part.shape[0], G, n, words, qval, qnn, ws=ws)
                 call("trid_index_rerank_add_f32", _p(scores), 1, cols, part.shape[0], G, _p(qnn), _p(self._nn), n, alpha, _p(words), stream())
-            _deep_topk(_p(scores), 1, cols, part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
+            if distinct:
+                self._distinct_select(scores, part.shape[0], k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
+            else:
+                _deep_topk(_p(scores), 1, cols, part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
         return vals, rows
+
+    def search_reranked_pids(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64, pids [Q,k] i64): search_reranked over DISTINCT pids - a person's score is their best
+        re-ranked allowed row, the result the k best persons (1 <= k <= MAX_SHORTLIST_K = 1024; value descending, then row ascending,
+        inside a pid and between pids; fewer allowed pids than k end in (-inf, -1, -1) slots).  It is search_reranked with the final row
+        select replaced by the two steps of shortlist_pids (trid_index_group_best_f32, trid_topk_rows_deep_pairs_f32) on the
+        bonus-modified buffer: exact by construction.  alpha == 0.0 equals shortlist_pids bit for bit.  Needs pids and a current graph;
+        queries, normalize, mask and the capture rule: as search_reranked and shortlist_pids."""
+        vals, rows = self._reranked("search_reranked_pids", queries, k, alpha, normalize, mask, distinct=True)
+        pids = self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
+        return vals, rows, pids
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
@@ -815,7 +936,7 @@ class GalleryIndex:
         no graph whatever else it holds, as it always did."""
         rows = sd["rows"]
         if rows is None or rows.shape[0] == 0:
-            self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
+            self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok, self._gtab_ok = 0, None, 0, False, False, False
             self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0
             return
         if rows.shape[0] > MAX_ROWS:
@@ -835,7 +956,7 @@ class GalleryIndex:
         live = sd.get("live")
         if live is not None and (not torch.is_tensor(live) or live.numel() != n):
             raise ValueError("GalleryIndex.load_state_dict: live must hold one entry per row (%d)" % n)
-        self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok = 0, None, 0, False, False
+        self._n, self._has_pids, self._dead, self._words_ok, self._gids_ok, self._gtab_ok = 0, None, 0, False, False, False
         self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0
         self._reserve(n, x.device)
         self._rows[:n].copy_(x)

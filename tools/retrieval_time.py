@@ -8,6 +8,7 @@ positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, 
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
 usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]]
+                                       [--deep-distinct ROWS_PER_PID K [K ...]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -23,6 +24,14 @@ kernel, panels of 32 queries for Q > 32).  Each Q entry gains index_distinct_ms 
 index, timed in the same process alternating with the others.  Each Q entry gains index_k16_ms, shortlist_ms {K: median, min, max},
 shortlist_over_index {K: its median over the k = 16 search's median} and shortlist_split_ms {K: {entry point: ms}}: one more call
 with an event pair around every library call (the dense product, the deep select, the query packing), summed per entry point.
+--deep-distinct M K [K ...]: GalleryIndex.shortlist_pids(k=K) for each K on an index over the same gallery with M rows per pid (pid = a
+fixed random permutation of the rows // M) next to shortlist(k=K) of the plain index - the yardstick - timed in the same process
+alternating with the others.  Each Q entry gains shortlist_pids_ms and shortlist_pids_yardstick_ms {K: median, min, max},
+shortlist_pids_over_shortlist {K: ratio of the medians}, shortlist_pids_split_ms {K: {entry point: ms}} (the dense product, trid_index_
+group_best_f32, trid_topk_rows_deep_pairs_f32, the query packing) and, for Q <= 32, shortlist_pids_bytes / shortlist_pids_floor_ms: the
+P16 gallery read, the score buffer written and read, the order read, the best-pair buffers written and read, at 6.3 TB/s.  The line
+gains deep_distinct_one_pid: the documented worst case, ONE pid holding a gallery of 1e5 rows (one wave walks it), k = 100, per Q the
+median of shortlist_pids and the time of the group-best pass alone.
 --rerank K [K ...]: GalleryIndex.build_neighbours(5) timed once (build_neighbours_ms), then search_reranked(k=K) and shortlist(k=K) of the
 same index for each K, timed in the same process alternating with the others.  Each Q entry gains reranked_ms and reranked_shortlist_ms
 {K: median, min, max}, reranked_over_shortlist {K: ratio of the medians}, reranked_split_ms {K: {entry point: ms}} (the bonus pass is
@@ -54,6 +63,15 @@ def index_main(argv):
         given = i + 1 < len(argv) and not argv[i + 1].startswith("--")
         distinct = int(argv[i + 1]) if given else 4
         argv = argv[:i] + argv[i + (2 if given else 1):]
+    deep_distinct, dd_rows = [], 0
+    if "--deep-distinct" in argv:  # (the first bare number after it is the rows per pid, every further one a K)
+        i = argv.index("--deep-distinct")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            deep_distinct.append(int(argv[j]))
+            j += 1
+        dd_rows, deep_distinct = deep_distinct[0], deep_distinct[1:]
+        argv = argv[:i] + argv[j:]
     deep = []
     if "--deep" in argv:  # (every bare number after --deep is a K, up to the next option)
         i = argv.index("--deep")
@@ -116,6 +134,12 @@ def index_main(argv):
         idx_d.add(g_raw, pids=torch.randperm(G, generator=gen) // distinct)
         line["distinct_rows_per_pid"] = distinct
         torch.cuda.synchronize()
+    idx_dd = None
+    if deep_distinct:
+        idx_dd = GalleryIndex(capacity=G)
+        idx_dd.add(g_raw, pids=torch.randperm(G, generator=gen) // dd_rows)
+        line["deep_distinct_rows_per_pid"] = dd_rows
+        torch.cuda.synchronize()
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -123,6 +147,20 @@ def index_main(argv):
         fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t) * 1e3
+
+    def split_of(fn):
+        """one more call with an event pair around every library call, summed per entry point"""
+        from textreid_amd import lib as LIB
+
+        torch.cuda.synchronize()
+        LIB.TRACE = []
+        fn()
+        torch.cuda.synchronize()
+        trace, LIB.TRACE = LIB.TRACE, None
+        split = {}
+        for name, _, e0, e1 in trace:
+            split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
+        return split
 
     for Q in Qs:
         q_raw = (torch.randn(Q, 256, generator=gen) * 3.0).cuda()
@@ -140,6 +178,9 @@ def index_main(argv):
             forms["index_k16"] = lambda: idx.search(q_raw, 16)
         for kd in deep:
             forms["shortlist_k%d" % kd] = lambda kd=kd: idx.shortlist(q_raw, kd)
+        for kp in deep_distinct:
+            forms["shortlist_k%d" % kp] = lambda kp=kp: idx.shortlist(q_raw, kp)
+            forms["shortlist_pids_k%d" % kp] = lambda kp=kp: idx_dd.shortlist_pids(q_raw, kp)
         for kr in rerank:
             forms["shortlist_k%d" % kr] = lambda kr=kr: idx.shortlist(q_raw, kr)
             forms["reranked_k%d" % kr] = lambda kr=kr: idx.search_reranked(q_raw, kr)
@@ -167,6 +208,17 @@ def index_main(argv):
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
         if idx_d is not None:
             ent["distinct_over_index"] = ent["index_distinct_ms"]["median"] / ent["index_ms"]["median"]
+        if deep_distinct:
+            later = set(deep) | set(rerank)  # (their blocks below take the shortlist entry out)
+            ent["shortlist_pids_ms"] = {str(kp): ent.pop("shortlist_pids_k%d_ms" % kp) for kp in deep_distinct}
+            ent["shortlist_pids_yardstick_ms"] = {str(kp): ent["shortlist_k%d_ms" % kp] if kp in later else ent.pop("shortlist_k%d_ms" % kp) for kp in deep_distinct}
+            ent["shortlist_pids_over_shortlist"] = {str(kp): ent["shortlist_pids_ms"][str(kp)]["median"] / ent["shortlist_pids_yardstick_ms"][str(kp)]["median"]
+                                                    for kp in deep_distinct}
+            ent["shortlist_pids_split_ms"] = {str(kp): split_of(lambda kp=kp: idx_dd.shortlist_pids(q_raw, kp)) for kp in deep_distinct}
+            if Q <= 32:  # the P16 gallery read, the score buffer written and read, the order read, the best pairs written and read
+                cols, n_pids = idx_dd._ws["scores"].shape[1], idx_dd._ws["gtable"][2]
+                ent["shortlist_pids_bytes"] = G * 1024 + 2 * G * cols * 4 + G * 4 + 2 * 2 * n_pids * 32 * 4
+                ent["shortlist_pids_floor_ms"] = ent["shortlist_pids_bytes"] / HBM * 1e3
         if rerank:
             from textreid_amd import lib as LIB
 
@@ -212,6 +264,20 @@ def index_main(argv):
         ent["rows_equal_parent"] = bool(torch.equal(a[1], b[1]))
         ent["max_dv_parent"] = float((a[0] - b[0]).abs().max())
         line["Q"][str(Q)] = ent
+    if deep_distinct:  # the documented worst case of the group-best pass: one pid holds the whole gallery, one wave walks it
+        rows_1 = 100000
+        one = GalleryIndex(capacity=rows_1)
+        one.add(g_raw[:rows_1], pids=torch.zeros(rows_1, dtype=torch.int64))
+        worst = {"rows": rows_1, "k": 100, "Q": {}}
+        for Q in Qs:
+            q_raw = (torch.randn(Q, 256, generator=gen) * 3.0).cuda()
+            fn = lambda: one.shortlist_pids(q_raw, 100)  # noqa: E731 (one real result, then 99 (-inf, -1, -1) slots)
+            for _ in range(WARM):
+                fn()
+            ts = sorted(timed(fn) for _ in range(CALLS))
+            worst["Q"][str(Q)] = {"shortlist_pids_ms": {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1]},
+                                  "group_best_ms": split_of(fn).get("trid_index_group_best_f32")}
+        line["deep_distinct_one_pid"] = worst
     if refresh:  # last: it changes the index (rows appended, rows removed)
         from textreid_amd import lib as LIB
 
