@@ -846,6 +846,26 @@ int trid_topk_rows_deep_pairs_f32(const float* val, const int32_t* col, long lon
 int trid_index_group_best_f32(const float* scores, long long ld_q, long long ld_g, int Q, int G, const int32_t* order,
                               const int32_t* starts, int n_groups, int n_slots, const uint32_t* mask_words, float* out_val,
                               int32_t* out_row, long long out_ld_q, long long out_ld_g, void* stream);
+/* List merge (csrc/index_merge.hip; the merge step of GalleryShards, textreid_amd/index_shards.py): per query, n_lists candidate
+ * lists of k_in entries each - val fp32, row int64 and optionally pid int64, all [Q, n_lists, k_in] contiguous - become the first k
+ * of their union in the library's one order.  row is the list's LOCAL row as the index entry points return it; row < 0 = the slot is
+ * ABSENT whatever its value.  The global row of a present candidate is list_base[s] + row (list_base int64 [n_lists], NULL = zeros);
+ * the global rows of one query's present candidates are distinct (the caller's contract); the lists need NOT be sorted.  Order: value
+ * descending by float comparison, then global row ascending; +0 == -0 tie by row and the original bits come back (the merge moves
+ * values and never computes one); a real -inf on a present row is an ordinary value that sorts last; NaN undefined.
+ *   pid == NULL (rows form): the result is the first k present candidates; out_pid is not touched (may be NULL).
+ *   pid != NULL (distinct form): a candidate counts only if no earlier candidate in the order has the same pid; the result is the
+ *     first k that count, out_pid [Q, k] their pids.
+ * out_val fp32 [Q, k], out_row int64 [Q, k] GLOBAL rows; a query with fewer than k results ends in (-inf, -1[, -1]) slots.
+ * 1 <= k <= 1024, 1 <= n_lists * k_in <= trid_index_merge_max_candidates() = 8192, k <= n_lists * k_in, 1 <= Q < 2^22 (one workgroup
+ * per query); val / out_val 4-byte, every int64 pointer 8-byte aligned.  More candidates are merged in rounds by the caller: merging
+ * groups of lists and then the results is exact for both forms.  One workgroup orders a query's candidates
+ * in LDS (16 bytes per slot of next_pow2(n_lists * k_in)).  Device contents are not validated and cannot fault: nothing read from row
+ * or pid is ever used as an address.  No host read, no allocation, one launch that depends on (n_lists, k_in, k) only: it can be
+ * captured - after ONE eager call on the device with any arguments, which raises the dynamic-LDS limit of every instantiation. */
+int trid_index_merge_max_candidates(void);
+int trid_index_merge_lists_f32(const float* val, const int64_t* row, const int64_t* list_base, const int64_t* pid, int Q, int n_lists,
+                               int k_in, int k, float* out_val, int64_t* out_row, int64_t* out_pid, void* stream);
 /* The k-reciprocal bonus of GalleryIndex.search_reranked (csrc/index_rerank.hip), IN PLACE on a score matrix addressed as in the deep
  * select above (element (q, g) = scores[q * ld_q + g * ld_g], the [G, cols] product and row-major [Q, G] both work, aliasing strides
  * are refused), between the dense product and the select.  qnn [Q, n] int64: each query's own neighbour rows (the out_idx of a deep

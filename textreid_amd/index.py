@@ -99,7 +99,9 @@ An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torc
 A recorded search answers against the gallery as it stood at the capture (row count, storage, tombstones and neighbour graph are
 part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours`` / ``refresh_neighbours``.
 
-Not built: gallery shards over ranks, widths other than 256, in-place re-embedding of a row, an
+More than ``MAX_ROWS`` rows, or one part per rank: ``GalleryShards`` (textreid_amd/index_shards.py) composes
+plain indexes and merges their lists exactly.
+Not built: widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
 or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
 pass); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).

@@ -8,7 +8,7 @@ positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, 
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
 usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]]
-                                       [--deep-distinct ROWS_PER_PID K [K ...]]
+                                       [--deep-distinct ROWS_PER_PID K [K ...]] [--shards S]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -42,7 +42,12 @@ timed again (remove_refresh_ms, remove_counts) - each one call after one untimed
 a second time with an event pair around every library call of the refresh (add_split_ms / remove_split_ms per entry point).  Next to them
 build_over_add_refresh / build_over_remove_refresh (build_neighbours_ms over each) and add_floor_ms: the bytes a refresh after the add
 needs (per group of 32 new rows: the old P16 rows for the product and the gallery for the search pass, the candidate buffer written and
-read, lists and values read and written) at 6.3 TB/s."""
+read, lists and values read and written) at 6.3 TB/s.
+--shards S: the same searches through GalleryShards (textreid_amd/index_shards.py, the in-process form) with S equal parts over the same
+gallery, 4 rows per pid, next to one plain GalleryIndex with the same pids, timed in the same process alternating with the others:
+search(k = 10), shortlist(k = 100) and shortlist_pids(k = 100).  Each Q entry gains shards_ms and shards_plain_ms {method: median, min,
+max}, shards_over_plain {method: ratio of the medians}, shards_split_ms {method: {entry point: ms}} (the merge is
+trid_index_merge_lists_f32) and shards_equal_plain {method: the values bit for bit and the mapped rows equal}."""
 import json, os, sys, time
 import torch
 
@@ -96,6 +101,11 @@ def index_main(argv):
             refresh.append(int(argv[j]))
             j += 1
         argv = argv[:i] + argv[j:]
+    shards = 0
+    if "--shards" in argv:
+        i = argv.index("--shards")
+        shards = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
     masked = None
     if "--masked" in argv:
         i = argv.index("--masked")
@@ -139,6 +149,20 @@ def index_main(argv):
         idx_dd = GalleryIndex(capacity=G)
         idx_dd.add(g_raw, pids=torch.randperm(G, generator=gen) // dd_rows)
         line["deep_distinct_rows_per_pid"] = dd_rows
+        torch.cuda.synchronize()
+    idx_s = sh = None
+    SHARD_FORMS = (("search", K), ("shortlist", 100), ("shortlist_pids", 100))
+    if shards:
+        from textreid_amd import GalleryShards
+        from textreid_amd.index_shards import SHARD_STRIDE
+
+        shard_rows = (G + shards - 1) // shards
+        pids_s = torch.randperm(G, generator=gen) // 4
+        idx_s = GalleryIndex(capacity=G)
+        idx_s.add(g_raw, pids=pids_s)
+        sh = GalleryShards(shard_rows=shard_rows)
+        sh.add(g_raw, pids=pids_s)
+        line["shards"], line["shard_rows"], line["shards_rows_per_pid"] = sh.n_shards, shard_rows, 4
         torch.cuda.synchronize()
 
     def timed(fn):
@@ -184,6 +208,9 @@ def index_main(argv):
         for kr in rerank:
             forms["shortlist_k%d" % kr] = lambda kr=kr: idx.shortlist(q_raw, kr)
             forms["reranked_k%d" % kr] = lambda kr=kr: idx.search_reranked(q_raw, kr)
+        for name, ks in (SHARD_FORMS if shards else ()):
+            forms["shards_plain_%s" % name] = lambda name=name, ks=ks: getattr(idx_s, name)(q_raw, ks)
+            forms["shards_%s" % name] = lambda name=name, ks=ks: getattr(sh, name)(q_raw, ks)
         for fn in forms.values():
             for _ in range(WARM):
                 fn()
@@ -203,6 +230,16 @@ def index_main(argv):
             ent["index_over_floor"] = ent["index_ms"]["median"] / ent["hbm_floor_ms"]
         ent["raw_over_index"] = ent["topk_raw_ms"]["median"] / ent["index_ms"]["median"]
         ent["unit_over_index"] = ent["topk_unit_ms"]["median"] / ent["index_ms"]["median"]
+        if shards:
+            ent["shards_plain_ms"] = {name: ent.pop("shards_plain_%s_ms" % name) for name, _ in SHARD_FORMS}
+            ent["shards_ms"] = {name: ent.pop("shards_%s_ms" % name) for name, _ in SHARD_FORMS}
+            ent["shards_over_plain"] = {name: ent["shards_ms"][name]["median"] / ent["shards_plain_ms"][name]["median"] for name, _ in SHARD_FORMS}
+            ent["shards_split_ms"] = {name: split_of(lambda name=name, ks=ks: getattr(sh, name)(q_raw, ks)) for name, ks in SHARD_FORMS}
+            ent["shards_equal_plain"] = {}
+            for name, ks in SHARD_FORMS:  # (more than 32 queries: the plain search takes the streaming route, whose values differ in the last bits)
+                a, b = getattr(sh, name)(q_raw, ks), getattr(idx_s, name if Q <= 32 or name != "search" else "shortlist")(q_raw, ks)
+                rows = (b[1] // shard_rows) * SHARD_STRIDE + b[1] % shard_rows
+                ent["shards_equal_plain"][name] = bool(torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], rows))
         if idx_m is not None:
             ent["masked_over_index"] = ent["index_masked_ms"]["median"] / ent["index_ms"]["median"]
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
