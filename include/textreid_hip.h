@@ -895,6 +895,27 @@ int trid_index_rerank_add_f32(float* scores, long long ld_q, long long ld_g, int
  * ld_cand >= rows when m > 0, cand / nn / nn_val 4-byte aligned.  No host read, no allocation, one launch. */
 int trid_index_nn_merge_f32(const float* cand, long long ld_cand, int m, int cand_first, int rows, const uint8_t* live, int32_t* nn,
                             float* nn_val, int n, uint8_t* redo, void* stream);
+/* The merge step of GalleryShards.refresh_neighbours (csrc/index_shard_graph.hip): the merge above for lists of GLOBAL row ids,
+ * id = shard * 2^21 + local row, of the rows [0, rows) of shard self_shard.  Two differences:
+ *   (a) liveness by global id.  live_all uint8 [live_bytes]: the shards' liveness bytes concatenated; shard s owns
+ *       live_all[live_off[s] .. live_off[s] + live_len[s]) (live_off int64 [n_shards], live_len int32 [n_shards], both on the device).
+ *       An id e decodes as s = e >> 21, l = e & (2^21 - 1) and counts as REMOVED when s >= n_shards, l >= live_len[s], live_off[s] + l
+ *       lies outside [0, live_bytes) or the byte is 0.  Nothing is read through an id that fails a range check: device contents
+ *       cannot fault.  Own row i is the id (self_shard, i); candidate j is the id cand_first + j - consecutive local rows of one
+ *       shard - and is skipped when it counts as removed.
+ *   (b) the order is the full one: a candidate goes in front of an entry iff its value is greater by float comparison, or the values
+ *       are equal and its global id is lower (+0 == -0); an absent entry (< 0) is behind every candidate.  Candidates may be numbered
+ *       below stored rows.  The caller's contract: a candidate is in no list yet.
+ * Per row i < rows, as above: own row removed -> all n slots (-1, -inf), redo[i] = 0; nn[i, 0] < 0 or an entry e >= 0 that counts as
+ * removed -> redo[i] = 1, list and values NOT written; else redo[i] = 0 and every live candidate is inserted, the last entry falls
+ * off, values move with their rows and keep their bits.  cand[j * ld_cand + i] = the similarity of row i (as the query) to
+ * candidate j; m == 0 with cand == NULL is the pure-removal pass.  Nothing outside nn / nn_val [0, rows) x [0, n) and redo [0, rows)
+ * is written.  1 <= n <= 8, m >= 0, 1 <= n_shards <= 1023 (the ids are int32), 0 <= self_shard < n_shards, 1 <= rows <= 2^21 - 1,
+ * cand_first >= 0 and (cand_first & (2^21 - 1)) + m <= 2^21 - 1, live_bytes >= 1, ld_cand >= rows when m > 0; cand / nn / nn_val /
+ * live_len 4-byte, live_off 8-byte aligned.  One row per lane, no LDS.  No host read, no allocation, one launch. */
+int trid_index_nn_merge_sharded_f32(const float* cand, long long ld_cand, int m, int cand_first, int rows, const uint8_t* live_all,
+                                    const int64_t* live_off, const int32_t* live_len, long long live_bytes, int n_shards, int self_shard,
+                                    int32_t* nn, float* nn_val, int n, uint8_t* redo, void* stream);
 /* per-row full descending argsort (rank(get_mAP=True), evaluation.py:14), ties -> lower column first.  G <= 16384:
  * one in-LDS bitonic sort per row, no workspace (ws may be NULL).  Larger rows: packed keys + rocPRIM segmented radix
  * sort in the caller's workspace of trid_argsort_ws_bytes(Q, G) bytes (256-byte aligned; 0 = none needed, or Q*G >= 2^31:

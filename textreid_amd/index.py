@@ -100,7 +100,8 @@ A recorded search answers against the gallery as it stood at the capture (row co
 part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours`` / ``refresh_neighbours``.
 
 More than ``MAX_ROWS`` rows, or one part per rank: ``GalleryShards`` (textreid_amd/index_shards.py) composes
-plain indexes and merges their lists exactly.
+plain indexes and merges their lists exactly; its neighbour graph over all shards and its re-ranked searches (section 7m) run the
+private steps of ``_reranked`` below (``_rerank_plan``, ``_panel_scores``, ``_rerank_own_lists``, ``_rerank_bonus``, ``_rerank_select``).
 Not built: widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
 or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
@@ -604,11 +605,12 @@ class GalleryIndex:
         ops.gemm_p16(gallery, ops.P16(wide, self._unit), scores, G, cols, self.dim, cols)
         return scores
 
-    def _deep_workspace(self, *ks, slots=None):
-        """the cached workspace of the deep select, large enough for a panel of 32 queries at every k given over the rows - and, with
-        ``slots`` = (n_slots, k), for the pairs select of k over n_slots group slots as well"""
+    def _deep_workspace(self, *ks, slots=None, rows=None):
+        """the cached workspace of the deep select, large enough for a panel of 32 queries at every k given over the rows (``rows``:
+        another extent than len) - and, with ``slots`` = (n_slots, k), for the pairs select of k over n_slots group slots as well"""
         L = ops.L.load()
-        nws = max([L.trid_topk_rows_deep_ws_bytes(SMALL_Q, self._n, k, 0) for k in ks] +
+        G = self._n if rows is None else rows
+        nws = max([L.trid_topk_rows_deep_ws_bytes(SMALL_Q, G, k, 0) for k in ks] +
                   ([L.trid_topk_rows_deep_ws_bytes(SMALL_Q, slots[0], slots[1], 0)] if slots else []))
         ws = self._ws.get("deep")
         if ws is None or ws.numel() < nws:
@@ -869,32 +871,61 @@ class GalleryIndex:
         query's own list and the bonus pass are shared; the final select is the deep row select or the two steps of shortlist_pids"""
         x = self._check_search(name, queries, k, mask, need_pids=distinct, max_k=MAX_SHORTLIST_K, need_graph=True)
         alpha = float(alpha)
-        Q, G, n = x.shape[0], self._n, self._nn.shape[1]
+        Q, n = x.shape[0], self._nn.shape[1]
         vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
         rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
-        L = ops.L.load()
-        if distinct:
-            table, n_slots, best = self._distinct_setup(k)
-            ws = self._deep_workspace(n, slots=(n_slots, k))
-        else:
-            ws = self._deep_workspace(k, n)
+        plan = self._rerank_plan(k, n, mask, distinct)
         if alpha != 0.0:
             qnn = torch.empty(min(Q, SMALL_Q), n, dtype=torch.int64, device=x.device)
             qval = torch.empty(min(Q, SMALL_Q), n, dtype=torch.float32, device=x.device)
         for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
             part = x[at : at + SMALL_Q]
-            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
-            scores = self._dense_scores(q16)
-            cols = scores.shape[1]
+            scores = self._panel_scores(part, normalize)
             if alpha != 0.0:
-                _deep_topk(_p(scores), 1, cols, part.shape[0], G, n, words, qval, qnn, ws=ws)
-                call("trid_index_rerank_add_f32", _p(scores), 1, cols, part.shape[0], G, _p(qnn), _p(self._nn), n, alpha, _p(words), stream())
-            if distinct:
-                self._distinct_select(scores, part.shape[0], k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
-            else:
-                _deep_topk(_p(scores), 1, cols, part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
+                self._rerank_own_lists(plan, scores, part.shape[0], n, qval, qnn)
+                self._rerank_bonus(plan, scores, part.shape[0], qnn, self._nn, n, alpha)
+            self._rerank_select(plan, scores, part.shape[0], k, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
         return vals, rows
+
+    # the private steps of a re-ranked search: _reranked above runs them on one index, GalleryShards (index_shards.py) runs them in two
+    # phases over its parts with the merge of the parts' lists between them.
+    def _rerank_plan(self, k, n, mask, distinct, extent=0):
+        """what every panel of one re-ranked search shares -> (G, words, ws, distinct state or None).  G = the rows the selects and the
+        bonus pass walk: len, or ``extent`` when that is more (GalleryShards: a part with fewer rows than the graph's n is walked as
+        ``extent`` = n rows, the extra ones masked off - the allow words are then always given, and they are zero behind len).
+        words: the allow words of ``live & mask``, None when every row is allowed; ws: the deep select's workspace for k and n over
+        G rows (and the pairs select of the distinct form)."""
+        G = max(self._n, extent)
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead or G > self._n) else None
+        if distinct:
+            table, n_slots, best = self._distinct_setup(k)
+            return G, words, self._deep_workspace(n, slots=(n_slots, k), rows=G), (table, n_slots, best)
+        return G, words, self._deep_workspace(k, n, rows=G), None
+
+    def _panel_scores(self, part, normalize):
+        """at most 32 queries -> the cached score buffer holding their dense product with the gallery (shortlist's first step)"""
+        q16, _ = self._query_panel(part, normalize, ops.L.load().trid_index_search_ws_bytes(self._n, SMALL_Q, MAX_K, 0))
+        return self._dense_scores(q16)
+
+    def _rerank_own_lists(self, plan, scores, Q, n, qval, qnn):
+        """the queries' own neighbour lists: a deep select with k = n over the allowed rows of the score buffer -> qval fp32, qnn int64 [Q, n]"""
+        G, words, ws, _ = plan
+        _deep_topk(_p(scores), 1, scores.shape[1], Q, G, n, words, qval, qnn, ws=ws)
+
+    def _rerank_bonus(self, plan, scores, Q, qnn, gnn, n, alpha):
+        """trid_index_rerank_add_f32 in place on the score buffer: qnn int64 [Q, n] the queries' lists, gnn int32 [>= G, n] the rows' lists
+        (the same id space: local rows here, global ids over shards)"""
+        G, words, _, _ = plan
+        call("trid_index_rerank_add_f32", _p(scores), 1, scores.shape[1], Q, G, _p(qnn), _p(gnn), n, alpha, _p(words), stream())
+
+    def _rerank_select(self, plan, scores, Q, k, vals, rows):
+        """the final select over the (modified) score buffer: the deep row select, or the two distinct-pid steps"""
+        G, words, ws, distinct = plan
+        if distinct is not None:
+            table, n_slots, best = distinct
+            self._distinct_select(scores, Q, k, words, table, n_slots, best, ws, vals, rows)
+        else:
+            _deep_topk(_p(scores), 1, scores.shape[1], Q, G, k, words, vals, rows, ws=ws)
 
     def search_reranked_pids(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
         """-> (values [Q,k] f32, rows [Q,k] i64, pids [Q,k] i64): search_reranked over DISTINCT pids - a person's score is their best

@@ -1,6 +1,6 @@
 """GalleryShards: exact search over a gallery that is held as several ``GalleryIndex`` parts - in one process (more rows than the
 ``MAX_ROWS`` = 2**21 - 1 of one index: the 31-bit byte offsets of the P16 retrieval kernels) or one part per rank of the default
-process group.  DESIGN.md section 7l.
+process group.  DESIGN.md sections 7l (the searches) and 7m (the neighbour graph and the re-ranked search).
 
 It composes plain ``GalleryIndex`` parts and adds ONE step, the merge of the parts' lists (``trid_index_merge_lists_f32``,
 csrc/index_merge.hip).  An index normalises and packs every row alone with the fixed unit scale, and its one-pass kernels and
@@ -38,7 +38,37 @@ with no live row contributes an absent list.  With one shard in the in-process f
     groups of lists first, then the groups' results - exact for both forms (section 7l).
 
 ``remove(rows=global rows | pids=...)``: each part applies what it owns; in the by-rank form every rank may pass the same arguments
-and rows of other ranks are skipped.  ``state_dict()`` / ``load_state_dict()``: the parts' own dicts plus ``shard_rows``.
+and rows of other ranks are skipped.  ``state_dict()`` / ``load_state_dict()``: the parts' own dicts plus ``shard_rows``, and the
+lists and values of a CURRENT neighbour graph (a dict written before the graph existed loads with no graph).
+
+The neighbour graph and the re-ranked search (section 7m).  A part's own ``GalleryIndex.build_neighbours`` keeps its local meaning and
+is not used here: a row's n nearest rows may lie in another part, and the k-reciprocal bonus compares lists of row ids that must mean
+the same thing everywhere.  The graph over ALL shards lives on this object: per part int32 ``[capacity_s, n]`` lists of GLOBAL row
+ids (they fit int32 up to ``MAX_GRAPH_SHARDS`` = 1023 shards; more is a ValueError of ``build_neighbours``) and their fp32 values;
+``neighbours`` / ``neighbour_values`` (one ``[len_s, n]`` tensor per part), ``neighbours_current`` (false after any ``add`` / ``remove``,
+told by the parts' row and removal counts), ``neighbours_refreshable``.  The definition is the same sentence: ONE GalleryIndex over the
+concatenated rows has these lists (ids after the mapping), these values bit for bit, and these re-ranked results.
+  * ``build_neighbours(n=5)``: for every panel of 32 consecutive rows of a part (in place in its P16 storage; a ragged panel through a
+    cached zero-padded one) one one-pass search per part at ``k = min(n, live rows of that part)`` (the masked form once it has
+    removed rows), the candidates staged ``[32, n_shards, n]``, ONE merge launch with the parts' bases, narrowed to int32.  No host
+    read.  By rank: collective - in round i every rank contributes the panel of its rows ``[32 i, 32 i + 32)``, searches its part with
+    every rank's panel, the lists are gathered, and a rank merges and keeps the lists of its own rows.
+  * ``search_reranked`` / ``search_reranked_pids`` (signatures and tuples of the index), per panel of 32 queries.  Phase 1 in every
+    part: the dense product into the part's cached score buffer and a deep select with k = n over the allowed rows; the parts' lists
+    merged into the query's own GLOBAL list.  Phase 2 in every part: ``trid_index_rerank_add_f32`` in place with that list and the
+    part's global-id lists, then the final deep select (or the two distinct-pid steps); the lists merged as ``shortlist`` /
+    ``shortlist_pids`` merge theirs.  Both run the private steps of ``GalleryIndex._reranked``.  ``alpha == 0.0`` is ``shortlist`` /
+    ``shortlist_pids``.  A part with fewer rows than n (a freshly opened last part) is walked as n rows whose extra rows are masked
+    off: the bonus kernel's and the select's ``n <= G`` rule stays as it is, the allow words are zero behind ``len`` and the stored
+    lists there are -1 (an index's buffers always hold at least 64 rows, so nothing has to grow).  In-process, after one eager call
+    a search allocates nothing but its outputs, the queries' lists and the parts' select outputs: it can be recorded.  By rank: a
+    gather and a merge after each phase; not capturable.
+  * ``refresh_neighbours()`` -> ``(new_rows, redone_rows)``, in-process only (by rank: RuntimeError naming ``build_neighbours``): per
+    part and per group of at most 32 new rows one ``trid_gemm_p16`` product (tile kernel, the group as A, the part's old rows as B)
+    and one ``trid_index_nn_merge_sharded_f32`` (csrc/index_shard_graph.hip: liveness by global id, order by value then global id -
+    the new rows of a middle part are numbered BELOW the stored rows of later parts); removals only: one launch per part with
+    m = 0; the new rows' lists from the build's panel step; the flags of all parts read once on the host, flagged rows gathered
+    32 at a time, recomputed by the panel step and scattered back.  Lists and values equal a fresh build bit for bit.
 
 Capture: in the in-process form, after one eager call a search reads nothing on the host and - while the candidates fit one merge
 launch - allocates nothing but its outputs: it can be recorded with ``torch.cuda.graph`` and replays against the current contents
@@ -46,18 +76,19 @@ of the queries and masks (record again after ``add`` / ``remove``, as for the in
 any case: the first merge on a device raises the dynamic-LDS limit of the kernel.  The by-rank form is NOT capturable: its searches
 are collectives.
 
-Not built: ``compact`` (it would renumber rows inside a part), the neighbour graph and the re-ranked search over shards,
-rebalancing rows between ranks, shards on several devices of one process.
+Not built: ``compact`` (it would renumber rows inside a part), the by-rank ``refresh_neighbours`` (the merge kernel's order rule is
+general, so it can be added), rebalancing rows between ranks, shards on several devices of one process.
 """
 
 import torch
 
 from . import ops, parallel
-from .index import DIM, MAX_K, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex
+from .index import DIM, MAX_K, MAX_NEIGHBOURS, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex
 from .ops import _p, call, stream
 
 SHARD_BITS = 21
 SHARD_STRIDE = 1 << SHARD_BITS  # global row = shard * SHARD_STRIDE + local row; MAX_ROWS = SHARD_STRIDE - 1
+MAX_GRAPH_SHARDS = 1023  # the neighbour graph holds global rows as int32: shard * SHARD_STRIDE + local < 2**31
 
 
 def _need_cuda(name, t):
@@ -102,6 +133,9 @@ class GalleryShards:
         self._parts = [GalleryIndex()]
         self._has_pids = None
         self._ws = {}  # the cached staging buffers of the merge and the shard bases
+        self._g_nn = None   # the neighbour graph over the shards: per part int32 [>= capacity_s, n] of GLOBAL rows (build_neighbours)
+        self._g_val = None  # per part fp32 [>= capacity_s, n]: the similarity of every entry (refresh_neighbours merges by them)
+        self._g_sig = None  # (len, removed rows) of every part when the graph was last current
 
     # ------------------------------------------------------------------ storage
     @property
@@ -223,8 +257,9 @@ class GalleryShards:
                 raise ValueError("GalleryShards.%s: the mask of shard %d must have shape [%d]; got %s" % (name, s + self.shard, len(part), tuple(m.shape)))
         return masks
 
-    def _check(self, name, queries, k, mask, max_k, distinct):
-        """the argument rules of the four searches, in the order of the index -> (queries fp32 contiguous, one mask per part)"""
+    def _check(self, name, queries, k, mask, max_k, distinct, need_graph=False):
+        """the argument rules of the searches, in the order of the index -> (queries fp32 contiguous, one mask per part).  need_graph:
+        a current neighbour graph, asked for after the argument rules and before the device's"""
         if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != DIM:
             raise ValueError("GalleryShards.%s: expected a [Q, %d] tensor" % (name, DIM))
         if distinct and self._has_pids is False:
@@ -234,6 +269,9 @@ class GalleryShards:
         masks = self._masks(name, mask)
         if queries.shape[0] == 0:
             raise ValueError("GalleryShards.%s: no queries" % name)
+        if need_graph and not self.neighbours_current:
+            raise RuntimeError("GalleryShards.%s: the neighbour graph is %s; call build_neighbours() first" % (
+                name, "absent" if self._g_nn is None else "stale (add / remove since it was built)"))
         _need_cuda(name, queries)
         return queries.contiguous().float(), masks
 
@@ -339,15 +377,395 @@ class GalleryShards:
         """-> (values, rows GLOBAL, pids), each [Q,k]: GalleryIndex.shortlist_pids over the shards, k <= 1024.  By-rank form: collective."""
         return self._search("shortlist_pids", queries, k, normalize, mask, MAX_SHORTLIST_K, True)
 
+    # ------------------------------------------------------------------ neighbour graph over the shards
+    def _sig(self):
+        """(len, removed rows) of every part: what a graph is current FOR (add and remove change it, wherever they were called)"""
+        return [(len(p), p._dead) for p in self._parts]
+
+    @property
+    def neighbours(self):
+        """one int32 [len_s, n] tensor per part of this process: the neighbour lists as GLOBAL row ids, as build_neighbours /
+        refresh_neighbours (or load_state_dict) left them, -1 in every slot of a row that was removed then or appended since (views of
+        the storage: read-only); None when no graph is held"""
+        if self._g_nn is None:
+            return None
+        self._grow_graph()
+        return tuple(t[: len(p)] for t, p in zip(self._g_nn, self._parts))
+
+    @property
+    def neighbour_values(self):
+        """one fp32 [len_s, n] tensor per part: the similarity of every entry of ``neighbours`` (-inf in the slots that hold -1); None
+        when no values are held (no graph, or lists loaded without them)"""
+        if self._g_nn is None or self._g_val is None:
+            return None
+        self._grow_graph()
+        return tuple(t[: len(p)] for t, p in zip(self._g_val, self._parts))
+
+    @property
+    def neighbours_current(self):
+        """the lists describe the shards as they stand (no add / remove since): search_reranked takes them"""
+        return self._g_nn is not None and self._g_sig == self._sig()
+
+    @property
+    def neighbours_refreshable(self):
+        """lists and their values are both held: the in-process form's refresh_neighbours can bring the graph up to date"""
+        return self._g_nn is not None and self._g_val is not None
+
+    def _grow_graph(self):
+        """the graph storage follows the parts: one pair of [>= capacity_s, n] buffers per part, (-1, -inf) in every row no build or
+        refresh has written (parts opened and rows appended since)"""
+        n = self._g_nn[0].shape[1]
+        dev = next((p.device for p in self._parts if p.device is not None), self._g_nn[0].device)
+        for s, part in enumerate(self._parts):
+            want = max(part.capacity, MAX_NEIGHBOURS)
+            if s < len(self._g_nn) and self._g_nn[s].shape[0] >= want:
+                continue
+            nn = torch.full((want, n), -1, dtype=torch.int32, device=dev)
+            val = None if self._g_val is None else torch.full((want, n), float("-inf"), dtype=torch.float32, device=dev)
+            if s < len(self._g_nn):
+                held = self._g_nn[s].shape[0]
+                nn[:held].copy_(self._g_nn[s])
+                self._g_nn[s] = nn
+                if val is not None:
+                    val[:held].copy_(self._g_val[s])
+                    self._g_val[s] = val
+            else:
+                self._g_nn.append(nn)
+                if val is not None:
+                    self._g_val.append(val)
+
+    def _fill_panel(self, src, Q, dev):
+        """Q < 32 P16 rows into the shards' own cached zero-padded [32, 256] panel (bit copies: the rows carry the fixed unit scale)"""
+        q16 = self._ws.get("panel")
+        if q16 is None or q16.device != dev:
+            q16 = torch.zeros(SMALL_Q, DIM, dtype=torch.float32, device=dev)
+            self._ws["panel"], self._ws["panel_rows"] = q16, 0
+        q16.view(torch.int32)[:Q].copy_(src.view(torch.int32))
+        if Q < self._ws["panel_rows"]:
+            q16[Q : self._ws["panel_rows"]].zero_()
+        self._ws["panel_rows"] = Q
+        return q16
+
+    def _panel_tmp(self, n, dev):
+        """the cached contiguous outputs of one one-pass search at k <= n: fp32 and int64, 32 * n elements each"""
+        tmp = self._ws.get(("tmp", n))
+        if tmp is None or tmp[0].device != dev:
+            tmp = (torch.empty(SMALL_Q * n, dtype=torch.float32, device=dev), torch.empty(SMALL_Q * n, dtype=torch.int64, device=dev))
+            self._ws[("tmp", n)] = tmp
+        return tmp
+
+    @staticmethod
+    def _one_pass(part, panel, Q, kk, vals, rows):
+        """one one-pass search of ``part`` with the Q rows of ``panel`` as the queries, k = kk <= part.live_count -> vals / rows [Q, kk]
+        (local rows): the masked form once the part has removed rows, as GalleryIndex._neighbour_search"""
+        G = len(part)
+        L = ops.L.load()
+        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, SMALL_Q, kk, 0))
+        lists = part._workspace(need)[3]
+        if part._dead:
+            call("trid_index_search_masked_p16", _p(panel), _p(part._p16), _p(part._unit), _p(part._mask_words(None)), Q, G, kk, 0, _p(vals), _p(rows),
+                 _p(lists), 0, stream())
+        else:
+            call("trid_index_search_p16", _p(panel), _p(part._p16), _p(part._unit), Q, G, kk, 0, _p(vals), _p(rows), _p(lists), 0, stream())
+
+    def _graph_panel(self, panel, Q, n):
+        """the panel step of the build: the Q <= 32 P16 rows of ``panel`` as the queries of one one-pass search per part at k = min(n,
+        live rows of the part), the candidates staged as [Q, n_shards, n] and merged in one launch with the parts' bases -> (values
+        fp32 [Q, n], GLOBAL rows int64 [Q, n]).  No host read."""
+        parts = self._parts
+        dev = panel.device
+        (val, row, _), base = self._staging(SMALL_Q, len(parts), n, False, dev)
+        tv, tr = self._panel_tmp(n, dev)
+        for t, other in enumerate(parts):
+            kk = min(n, other.live_count) if len(other) else 0
+            if kk:
+                ov, orow = tv[: Q * kk].view(Q, kk), tr[: Q * kk].view(Q, kk)
+                self._one_pass(other, panel, Q, kk, ov, orow)
+                val[:Q, t, :kk].copy_(ov)
+                row[:Q, t, :kk].copy_(orow)
+            if kk < n:
+                row[:Q, t, kk:].fill_(-1)
+        return merge_lists(val[:Q], row[:Q], n, base)
+
+    def _graph_rows(self, s, first, last, n):
+        """the lists of the rows [first, last) of part s from scratch, into the graph storage: panels of 32 consecutive rows - in place
+        in the P16 storage, a ragged one through the cached zero-padded panel - through the panel step; (-1, -inf) for removed rows"""
+        part = self._parts[s]
+        nn, val = self._g_nn[s], self._g_val[s]
+        for at in range(first, last, SMALL_Q):
+            Q = min(SMALL_Q, last - at)
+            panel = part._p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part._p16[at : at + Q], Q, part.device)
+            v, r = self._graph_panel(panel, Q, n)
+            nn[at : at + Q].copy_(r)  # (narrowed: global ids of at most 1023 shards fit int32)
+            val[at : at + Q].copy_(v)
+        if part._dead:
+            dead = ~part._live[first:last, None]
+            nn[first:last].masked_fill_(dead, -1)
+            val[first:last].masked_fill_(dead, float("-inf"))
+
+    def _check_build(self, name, n):
+        if not isinstance(n, int) or n < 1 or n > MAX_NEIGHBOURS:
+            raise ValueError("GalleryShards.%s: n must be in [1, %d]; got %r" % (name, MAX_NEIGHBOURS, n))
+        if self.n_shards > MAX_GRAPH_SHARDS:
+            raise ValueError("GalleryShards.%s: the lists hold global rows as int32, which reach %d shards; the gallery has %d" % (
+                name, MAX_GRAPH_SHARDS, self.n_shards))
+
+    def build_neighbours(self, n=5):
+        """Build the neighbour graph over ALL shards: for every live row, the n best live rows of the whole gallery for the row's own
+        embedding as the query, as GLOBAL row ids (value descending, then global row ascending), with their values; (-1, -inf) in every
+        slot of a removed row.  Equal to GalleryIndex.build_neighbours of the concatenated gallery, values bit for bit, ids after the
+        mapping.  1 <= n <= 8, n <= the live rows of all shards, at most 1023 shards.  Per panel of 32 rows one
+        one-pass search per part and one merge launch; quadratic in the rows, no host read.  By-rank form: COLLECTIVE - every rank's
+        panels go to every rank (parallel.all_gather_rows), every rank searches its part, the lists are gathered and merged, every
+        rank keeps the lists of its own rows (the row counts are gathered and read once)."""
+        self._check_build("build_neighbours", n)
+        if self.collective and parallel.world_size() > 1:
+            return self._build_by_rank(n)
+        if len(self) == 0:
+            raise ValueError("GalleryShards.build_neighbours: the shards are empty")
+        if n > self.live_count:
+            raise ValueError("GalleryShards.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
+        dev = next(p.device for p in self._parts if len(p))
+        self._g_nn = [torch.full((max(p.capacity, MAX_NEIGHBOURS), n), -1, dtype=torch.int32, device=dev) for p in self._parts]
+        self._g_val = [torch.full((max(p.capacity, MAX_NEIGHBOURS), n), float("-inf"), dtype=torch.float32, device=dev) for p in self._parts]
+        self._g_sig = None
+        for s, part in enumerate(self._parts):
+            if len(part):
+                self._graph_rows(s, 0, len(part), n)
+        self._g_sig = self._sig()
+
+    def _build_by_rank(self, n):
+        """the collective build: in round i every rank contributes the panel of its rows [32 i, 32 i + 32) (zeros once it has none),
+        searches its part with every rank's panel, and the [W, 32, n] lists are gathered; a rank merges the W lists of its own panel"""
+        W, r = parallel.world_size(), parallel.rank()
+        part = self._parts[0]
+        dev = part.device if part.device is not None else torch.device("cuda", torch.cuda.current_device())
+        counts = parallel.all_gather_rows(torch.tensor([[len(part), part.live_count]], dtype=torch.int64, device=dev)).cpu()
+        if int(counts[:, 0].sum()) == 0:
+            raise ValueError("GalleryShards.build_neighbours: the shards are empty")
+        if n > int(counts[:, 1].sum()):
+            raise ValueError("GalleryShards.build_neighbours: n must be <= live_count = %d; got %d" % (int(counts[:, 1].sum()), n))
+        G = len(part)
+        kk = min(n, part.live_count) if G else 0
+        nn = torch.full((max(part.capacity, MAX_NEIGHBOURS), n), -1, dtype=torch.int32, device=dev)
+        val = torch.full((max(part.capacity, MAX_NEIGHBOURS), n), float("-inf"), dtype=torch.float32, device=dev)
+        zero = torch.zeros(SMALL_Q, DIM, dtype=torch.float32, device=dev)
+        cv = torch.empty(W * SMALL_Q, n, dtype=torch.float32, device=dev)
+        cr = torch.empty(W * SMALL_Q, n, dtype=torch.int64, device=dev)
+        tv, tr = self._panel_tmp(n, dev)
+        base = torch.arange(W, dtype=torch.int64, device=dev) * SHARD_STRIDE
+        for at in range(0, int(counts[:, 0].max()), SMALL_Q):
+            Q = max(0, min(SMALL_Q, G - at))
+            mine = zero if Q == 0 else part._p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part._p16[at : at + Q], Q, dev)
+            panels = parallel.all_gather_rows(mine.view(torch.int32)).view(torch.float32)  # [W * 32, 256]: bit copies of P16 rows
+            cr.fill_(-1)
+            for w in range(W):
+                Qw = max(0, min(SMALL_Q, int(counts[w, 0]) - at))
+                if Qw and kk:
+                    ov, orow = tv[: Qw * kk].view(Qw, kk), tr[: Qw * kk].view(Qw, kk)
+                    self._one_pass(part, panels[w * SMALL_Q : (w + 1) * SMALL_Q], Qw, kk, ov, orow)
+                    cv[w * SMALL_Q : w * SMALL_Q + Qw, :kk].copy_(ov)
+                    cr[w * SMALL_Q : w * SMALL_Q + Qw, :kk].copy_(orow)
+            # [source rank, panel owner, 32, n] -> this rank's panel: [32, source rank, n]
+            gv = parallel.all_gather_rows(cv).view(W, W, SMALL_Q, n)[:, r].permute(1, 0, 2).contiguous()
+            gr = parallel.all_gather_rows(cr).view(W, W, SMALL_Q, n)[:, r].permute(1, 0, 2).contiguous()
+            if Q:
+                v, rows = merge_lists(gv[:Q], gr[:Q], n, base)
+                nn[at : at + Q].copy_(rows)
+                val[at : at + Q].copy_(v)
+        if G and part._dead:
+            dead = ~part._live[:G, None]
+            nn[:G].masked_fill_(dead, -1)
+            val[:G].masked_fill_(dead, float("-inf"))
+        self._g_nn, self._g_val, self._g_sig = [nn], [val], self._sig()
+
+    def refresh_neighbours(self):
+        """Bring a stale graph up to date EXACTLY -> (new_rows, redone_rows): the live rows appended since the graph was last current,
+        and the older rows whose lists were recomputed because they held a row removed since.  Lists and values afterwards equal those
+        of a fresh build_neighbours(n) bit for bit.  In-process form only: the by-rank form raises a
+        RuntimeError (call build_neighbours again).  Needs ``neighbours_refreshable`` (RuntimeError naming build_neighbours) and
+        n <= live_count (the ValueError of build_neighbours); a current graph returns (0, 0) without a launch.  With the rows covered
+        so far as "old":
+          * per part s and per group of at most 32 new rows: the trid_gemm_p16 product (tile kernel) of the group's P16 rows as A with
+            part s's old P16 rows as B - the direction of the definition, old row as the query - into part s's cached score buffer,
+            then ONE trid_index_nn_merge_sharded_f32 launch; removals only: one launch per part with m = 0;
+          * the lists of the new rows from the build's panel step over their range;
+          * the flags of all parts are read once on the host; flagged rows are gathered 32 at a time into the cached panel, put
+            through the build's panel step and scattered back."""
+        if self.collective:
+            raise RuntimeError("GalleryShards.refresh_neighbours: the by-rank form has no refresh; call build_neighbours() again")
+        if not self.neighbours_refreshable:
+            raise RuntimeError("GalleryShards.refresh_neighbours: %s; call build_neighbours() first" % (
+                "there is no neighbour graph" if self._g_nn is None else "the neighbour graph was loaded without its values"))
+        n = self._g_nn[0].shape[1]
+        if n > self.live_count:
+            raise ValueError("GalleryShards.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
+        if self.neighbours_current:
+            return 0, 0
+        self._check_build("refresh_neighbours", n)
+        self._grow_graph()
+        parts, S = self._parts, len(self._parts)
+        lens = [len(p) for p in parts]
+        old = [min(c, g) for (c, _), g in zip(self._g_sig or [], lens)] + [0] * (S - len(self._g_sig or []))
+        dev = next(p.device for p in parts if len(p))
+        live_all = torch.cat([p._live[:g].view(torch.uint8) for p, g in zip(parts, lens) if g])  # (bool storage: one byte per row, 0 / 1)
+        offs = [sum(lens[:s]) for s in range(S)]
+        live_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+        live_len = torch.tensor(lens, dtype=torch.int32, device=dev)
+        groups = [(t, at, min(SMALL_Q, lens[t] - at)) for t in range(S) for at in range(old[t], lens[t], SMALL_Q)]
+        starts = [sum(old[:s]) for s in range(S + 1)]
+        redo = torch.zeros(max(starts[S], 1), dtype=torch.uint8, device=dev)
+        for s, part in enumerate(parts):
+            n0 = old[s]
+            if n0 == 0:
+                continue
+
+            def merge(cand, m, first):
+                call("trid_index_nn_merge_sharded_f32", _p(cand), n0, m, first, n0, _p(live_all), _p(live_off), _p(live_len), live_all.numel(), S, s,
+                     _p(self._g_nn[s]), _p(self._g_val[s]), n, _p(redo[starts[s] :]), stream())
+
+            if not groups:
+                merge(None, 0, 0)
+            for t, at, m in groups:
+                # the direction and the kernel of GalleryIndex._candidate_scores; the A panel comes from part t
+                cand = part._score_buffer(part._ws.get("cols", SMALL_Q))  # (capacity * cols >= 32 * n0 floats)
+                ops.gemm_p16(ops.P16(parts[t]._p16[at : at + m], parts[t]._unit), ops.P16(part._p16[:n0], part._unit), cand, m, n0, DIM, n0, tile_only=True)
+                merge(cand, m, t * SHARD_STRIDE + at)
+        for t in range(S):
+            if lens[t] > old[t]:
+                self._graph_rows(t, old[t], lens[t], n)
+        again = torch.nonzero(redo[: starts[S]]).reshape(-1).cpu()  # (the one host read: how many rows, and which)
+        for s, part in enumerate(parts):
+            own = (again[(again >= starts[s]) & (again < starts[s + 1])] - starts[s]).to(dev)
+            for at in range(0, own.numel(), SMALL_Q):
+                rows = own[at : at + SMALL_Q]
+                Q = rows.numel()
+                v, r = self._graph_panel(self._fill_panel(part._p16.view(torch.int32)[rows], Q, dev), Q, n)
+                self._g_nn[s][rows] = r.int()
+                self._g_val[s][rows] = v
+        new_rows = sum(int(parts[t]._live[old[t] : lens[t]].sum()) for t in range(S) if lens[t] > old[t])
+        self._g_sig = self._sig()
+        return new_rows, int(again.numel())
+
+    # ------------------------------------------------------------------ re-ranked search
+    def _combine(self, val, row, pid, base, k):
+        """the candidates of this process's parts, [Q, parts, kin] with LOCAL rows, -> the first k over all shards: one merge with the
+        parts' bases, or - by rank - a gather of every rank's [Q, kin] list first"""
+        if self.collective and parallel.world_size() > 1:
+            W = parallel.world_size()
+            Q, _, kin = val.shape
+            cand = [parallel.all_gather_rows(t.reshape(Q, kin)).view(W, Q, kin).permute(1, 0, 2).contiguous() for t in (val, row) + (() if pid is None else (pid,))]
+            base = torch.arange(W, dtype=torch.int64, device=val.device) * SHARD_STRIDE
+            return self._merge(cand[0], cand[1], None if pid is None else cand[2], base, k)
+        return self._merge(val, row, pid, base, k)
+
+    def _reranked(self, name, queries, k, alpha, normalize, mask, distinct):
+        """search_reranked (distinct=False) and search_reranked_pids (True): per panel of 32 queries, phase 1 in every part (the dense
+        product into the part's score buffer, the deep select with k = n, the lists merged into the query's own GLOBAL list), phase 2
+        in every part (the bonus pass in place with that list and the part's global-id lists, the final select, the lists merged) -
+        the private steps of GalleryIndex._reranked"""
+        x, masks = self._check(name, queries, k, mask, MAX_SHORTLIST_K, distinct, need_graph=True)
+        alpha = float(alpha)
+        if alpha == 0.0:  # (no bonus, and no select that only feeds it: the shortlist itself)
+            return self._search("shortlist_pids" if distinct else "shortlist", queries, k, normalize, mask, MAX_SHORTLIST_K, distinct)
+        self._grow_graph()
+        parts, S = self._parts, len(self._parts)
+        Q, dev, n = x.shape[0], x.device, self._g_nn[0].shape[1]
+        # a part is asked for min(k, what it holds), as in the other searches; one with no live row contributes absent lists.  A part
+        # with fewer rows than n is walked as n rows, the extra ones masked off (GalleryIndex._rerank_plan)
+        ks = [0 if len(p) == 0 or p.live_count == 0 else min(k, len(p) if m is not None else p.live_count) for p, m in zip(parts, masks)]
+        plans = [p._rerank_plan(kk, n, m, distinct, extent=n) if kk else None for p, m, kk in zip(parts, masks, ks)]
+        kin = k if self.collective else max(max(ks), -(-k // S))
+        outs = [torch.empty(Q, k, dtype=d, device=dev) for d in (torch.float32, torch.int64, torch.int64)[: 3 if distinct else 2]]
+        own = [(torch.empty(SMALL_Q, n, dtype=torch.float32, device=dev), torch.empty(SMALL_Q, n, dtype=torch.int64, device=dev)) if kk else None for kk in ks]
+        tmp = [(torch.empty(SMALL_Q * kk, dtype=torch.float32, device=dev), torch.empty(SMALL_Q * kk, dtype=torch.int64, device=dev)) if kk else None for kk in ks]
+        scores = [None] * S
+        for at in range(0, Q, SMALL_Q):
+            xp = x[at : at + SMALL_Q]
+            Qp = xp.shape[0]
+            (sv, sr, _), base = self._staging(Qp, S, n, False, dev)
+            for s, part in enumerate(parts):
+                if ks[s]:
+                    scores[s] = part._panel_scores(xp, normalize)
+                    qv, qn = own[s][0][:Qp], own[s][1][:Qp]
+                    part._rerank_own_lists(plans[s], scores[s], Qp, n, qv, qn)
+                    sv[:, s].copy_(qv)
+                    sr[:, s].copy_(qn)
+                else:
+                    sr[:, s].fill_(-1)
+            qnn = self._combine(sv, sr, None, base, n)[1]  # the queries' own lists, GLOBAL rows, int64 [Qp, n]
+            (fv, fr, fp), base = self._staging(Qp, S, kin, distinct, dev)
+            for s, part in enumerate(parts):
+                kk = ks[s]
+                if kk:
+                    part._rerank_bonus(plans[s], scores[s], Qp, qnn, self._g_nn[s], n, alpha)
+                    ov, orow = tmp[s][0][: Qp * kk].view(Qp, kk), tmp[s][1][: Qp * kk].view(Qp, kk)
+                    part._rerank_select(plans[s], scores[s], Qp, kk, ov, orow)
+                    fv[:, s, :kk].copy_(ov)
+                    fr[:, s, :kk].copy_(orow)
+                    if distinct:
+                        fp[:, s, :kk].copy_(part._pids[: len(part)][orow].masked_fill_(orow < 0, -1))
+                if kk < kin:
+                    fr[:, s, kk:].fill_(-1)
+            for dst, src in zip(outs, self._combine(fv, fr, fp, base, k)):
+                dst[at : at + Qp].copy_(src)
+        return tuple(outs)
+
+    def search_reranked(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64 GLOBAL): GalleryIndex.search_reranked over the shards - the exact k best allowed rows by
+        similarity + k-reciprocal bonus against the graph of build_neighbours, k <= 1024; a query with fewer than k allowed rows ends in
+        (-inf, -1) slots; alpha == 0.0 equals shortlist bit for bit.  Needs a current graph (RuntimeError naming build_neighbours).
+        In-process: capturable after one eager call.  By-rank form: collective."""
+        return self._reranked("search_reranked", queries, k, alpha, normalize, mask, False)
+
+    def search_reranked_pids(self, queries, k=10, alpha=0.05, normalize=True, mask=None):
+        """-> (values, rows GLOBAL, pids), each [Q,k]: GalleryIndex.search_reranked_pids over the shards - the k best distinct pids, each
+        by its best re-ranked allowed row; alpha == 0.0 equals shortlist_pids bit for bit.  By-rank form: collective."""
+        return self._reranked("search_reranked_pids", queries, k, alpha, normalize, mask, True)
+
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
-        """{"shard_rows", "collective", "parts": the parts' own state dicts in shard order} (by-rank form: this rank's one part)"""
-        return {"shard_rows": self.shard_rows, "collective": self.collective, "parts": [p.state_dict() for p in self._parts]}
+        """{"shard_rows", "collective", "parts": the parts' own state dicts in shard order (by-rank form: this rank's one part),
+        "neighbours" / "neighbour_values": one int32 / fp32 [len_s, n] tensor per part when the graph over the shards is current (the
+        values when they are held), None otherwise}"""
+        current = self.neighbours_current and len(self) != 0
+        nn, val = (self.neighbours, self.neighbour_values) if current else (None, None)
+        return {"shard_rows": self.shard_rows, "collective": self.collective, "parts": [p.state_dict() for p in self._parts],
+                "neighbours": None if nn is None else [t.clone() for t in nn], "neighbour_values": None if val is None else [t.clone() for t in val]}
+
+    @staticmethod
+    def _load_graph(parts, nn, val):
+        """the lists (and values) of a state dict, checked against the loaded parts -> the graph storage (lists, values or None)"""
+        ok = isinstance(nn, (list, tuple)) and len(nn) == len(parts) and all(
+            torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == len(p) and 1 <= t.shape[1] <= MAX_NEIGHBOURS and
+            t.shape[1] == nn[0].shape[1] for t, p in zip(nn, parts))
+        if not ok:
+            raise ValueError("GalleryShards.load_state_dict: neighbours must be one int32 [len, n] tensor per part with 1 <= n <= %d" % MAX_NEIGHBOURS)
+        if val is not None and not (isinstance(val, (list, tuple)) and len(val) == len(nn) and all(
+                torch.is_tensor(v) and v.dtype == torch.float32 and tuple(v.shape) == tuple(t.shape) for v, t in zip(val, nn))):
+            raise ValueError("GalleryShards.load_state_dict: neighbour_values must be one float32 tensor per part, shaped like neighbours")
+        if len(parts) > MAX_GRAPH_SHARDS:
+            raise ValueError("GalleryShards.load_state_dict: the lists hold global rows as int32, which reach %d shards; got %d" % (MAX_GRAPH_SHARDS, len(parts)))
+        dev = next((p.device for p in parts if p.device is not None), nn[0].device)
+        n = nn[0].shape[1]
+        g_nn, g_val = [], None if val is None else []
+        for s, part in enumerate(parts):
+            want = max(part.capacity, MAX_NEIGHBOURS)
+            a = torch.full((want, n), -1, dtype=torch.int32, device=dev)
+            a[: len(part)].copy_(nn[s].to(dev))
+            g_nn.append(a)
+            if val is not None:
+                b = torch.full((want, n), float("-inf"), dtype=torch.float32, device=dev)
+                b[: len(part)].copy_(val[s].to(dev))
+                g_val.append(b)
+        return g_nn, g_val
 
     def load_state_dict(self, sd):
         """Replace the contents with the parts of ``sd`` (each loaded by GalleryIndex.load_state_dict; the row ids are those of the
-        saved shards).  shard_rows is taken from the dict; the form (collective or not) stays that of this object, and the by-rank
-        form takes exactly one part."""
+        saved shards).  "neighbours" present and not None: adopted as the current graph over the shards, refreshable when
+        "neighbour_values" came with them (both are checked before anything is replaced); a dict without the key (as written before
+        the graph existed) loads with no graph.  shard_rows is taken from the dict; the form (collective or not) stays that of this
+        object, and the by-rank form takes exactly one part."""
         parts = list(sd["parts"])
         shard_rows = int(sd["shard_rows"])
         if shard_rows < 1 or shard_rows > MAX_ROWS:
@@ -361,6 +779,9 @@ class GalleryShards:
             part = GalleryIndex()
             part.load_state_dict(one)
             loaded.append(part)
+        graph = (None, None) if sd.get("neighbours") is None else self._load_graph(loaded, sd["neighbours"], sd.get("neighbour_values"))
         self.shard_rows, self._parts, self._ws = shard_rows, loaded, {}
         held = [p._has_pids for p in loaded if len(p)]
         self._has_pids = held[0] if held else None
+        self._g_nn, self._g_val = graph
+        self._g_sig = None if graph[0] is None else self._sig()

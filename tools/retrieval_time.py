@@ -8,7 +8,7 @@ positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, 
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
 usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]]
-                                       [--deep-distinct ROWS_PER_PID K [K ...]] [--shards S]
+                                       [--deep-distinct ROWS_PER_PID K [K ...]] [--shards S [--shards-rerank] [--shards-refresh M [M ...]]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
 embeddings and similarity_topk(..., normalize=False) on unit rows (the two forms a caller without the index has).  One JSON line: the
@@ -47,7 +47,14 @@ read, lists and values read and written) at 6.3 TB/s.
 gallery, 4 rows per pid, next to one plain GalleryIndex with the same pids, timed in the same process alternating with the others:
 search(k = 10), shortlist(k = 100) and shortlist_pids(k = 100).  Each Q entry gains shards_ms and shards_plain_ms {method: median, min,
 max}, shards_over_plain {method: ratio of the medians}, shards_split_ms {method: {entry point: ms}} (the merge is
-trid_index_merge_lists_f32) and shards_equal_plain {method: the values bit for bit and the mapped rows equal}."""
+trid_index_merge_lists_f32) and shards_equal_plain {method: the values bit for bit and the mapped rows equal}.
+--shards-rerank (with --shards): build_neighbours(5) of the shards and of the plain index, each timed once (shards_build_neighbours_ms,
+shards_plain_build_neighbours_ms; shards_graph_equal_plain: lists after the id mapping and values bit for bit), and search_reranked(k = 10)
+as a fourth method of every entry above - the plain index over the same rows is the yardstick.
+--shards-refresh M [M ...] (with --shards; after the Q loop, it changes the shards): per M, M rows are appended and
+GalleryShards.refresh_neighbours() is timed (refresh_ms, counts), then build_neighbours(5) on the same contents (build_ms; refresh_equals_
+build: lists and values bit for bit), then M more rows and one refresh with an event pair around every library call (split_ms per entry
+point, and merge_launches / merge_ms_per_launch of trid_index_nn_merge_sharded_f32 alone) - each after one untimed warm-up refresh."""
 import json, os, sys, time
 import torch
 
@@ -101,6 +108,16 @@ def index_main(argv):
             refresh.append(int(argv[j]))
             j += 1
         argv = argv[:i] + argv[j:]
+    shards_rerank = "--shards-rerank" in argv
+    argv = [a for a in argv if a != "--shards-rerank"]
+    shards_refresh = []
+    if "--shards-refresh" in argv:  # (as --deep: every bare number after it is an M)
+        i = argv.index("--shards-refresh")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            shards_refresh.append(int(argv[j]))
+            j += 1
+        argv = argv[:i] + argv[j:]
     shards = 0
     if "--shards" in argv:
         i = argv.index("--shards")
@@ -151,7 +168,7 @@ def index_main(argv):
         line["deep_distinct_rows_per_pid"] = dd_rows
         torch.cuda.synchronize()
     idx_s = sh = None
-    SHARD_FORMS = (("search", K), ("shortlist", 100), ("shortlist_pids", 100))
+    SHARD_FORMS = (("search", K), ("shortlist", 100), ("shortlist_pids", 100)) + ((("search_reranked", K),) if shards_rerank else ())
     if shards:
         from textreid_amd import GalleryShards
         from textreid_amd.index_shards import SHARD_STRIDE
@@ -164,6 +181,18 @@ def index_main(argv):
         sh.add(g_raw, pids=pids_s)
         line["shards"], line["shard_rows"], line["shards_rows_per_pid"] = sh.n_shards, shard_rows, 4
         torch.cuda.synchronize()
+        if shards_rerank:  # the graph over the shards and the plain index's: S one-pass searches and one merge per panel of 32 rows
+            t0 = time.perf_counter()
+            sh.build_neighbours(5)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            idx_s.build_neighbours(5)
+            torch.cuda.synchronize()
+            line["shards_build_neighbours_ms"], line["shards_plain_build_neighbours_ms"] = (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
+            want = idx_s.neighbours.long()
+            want = torch.where(want < 0, want, (want // shard_rows) * SHARD_STRIDE + want % shard_rows)
+            line["shards_graph_equal_plain"] = bool(torch.equal(torch.cat(sh.neighbours).long(), want) and
+                                                    torch.equal(torch.cat(sh.neighbour_values).view(torch.int32), idx_s.neighbour_values.view(torch.int32)))
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -315,6 +344,41 @@ def index_main(argv):
             worst["Q"][str(Q)] = {"shortlist_pids_ms": {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1]},
                                   "group_best_ms": split_of(fn).get("trid_index_group_best_f32")}
         line["deep_distinct_one_pid"] = worst
+    if shards and shards_refresh:  # it changes the shards (rows appended: they open a part)
+        from textreid_amd import lib as LIB
+
+        def new_rows(M):
+            return (torch.randn(M, 256, generator=gen) * 3.0).cuda(), torch.arange(len(sh), len(sh) + M) // 4 + G
+
+        if not sh.neighbours_current:
+            line["shards_build_neighbours_ms"] = timed(lambda: sh.build_neighbours(5))
+        sh.add(*new_rows(1))  # warm-up: every kernel of a refresh has run once
+        sh.refresh_neighbours()
+        line["shards_refresh"] = {}
+        for M in shards_refresh:
+            rows_before = len(sh)
+            sh.add(*new_rows(M))
+            counts = []
+            ms = timed(lambda: counts.append(sh.refresh_neighbours()))
+            nn, val = [t.clone() for t in sh.neighbours], [t.clone() for t in sh.neighbour_values]
+            build_ms = timed(lambda: sh.build_neighbours(5))
+            same = all(torch.equal(a, b) for a, b in zip(nn, sh.neighbours)) and all(
+                torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(val, sh.neighbour_values))
+            sh.add(*new_rows(M))
+            torch.cuda.synchronize()
+            LIB.TRACE = []
+            sh.refresh_neighbours()
+            torch.cuda.synchronize()
+            trace, LIB.TRACE = LIB.TRACE, None
+            split, merges = {}, []
+            for name, _, e0, e1 in trace:
+                split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
+                if name == "trid_index_nn_merge_sharded_f32":
+                    merges.append(e0.elapsed_time(e1))
+            line["shards_refresh"][str(M)] = {"rows_before": rows_before, "shards_after": sh.n_shards, "refresh_ms": ms, "counts": list(counts[0]),
+                                              "build_ms": build_ms, "build_over_refresh": build_ms / ms, "refresh_equals_build": bool(same),
+                                              "split_ms": split, "merge_launches": len(merges),
+                                              "merge_ms_per_launch": sum(merges) / max(len(merges), 1)}
     if refresh:  # last: it changes the index (rows appended, rows removed)
         from textreid_amd import lib as LIB
 
