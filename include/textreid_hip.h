@@ -880,6 +880,36 @@ int trid_index_merge_lists_f32(const float* val, const int64_t* row, const int64
  * aligned.  No host read, no allocation, one launch: it can be captured. */
 int trid_index_rerank_add_f32(float* scores, long long ld_q, long long ld_g, int Q, int G, const int64_t* qnn, const int32_t* gnn,
                               int n, float alpha, const uint32_t* mask_words, void* stream);
+/* The blend of GalleryIndex.expand_queries / search_expanded / augmented (csrc/index_blend.hip): query expansion (AQE, and alpha-QE
+ * for power >= 1) and database-side augmentation around the normalise-and-match step of lib/data/metrics/evaluation.py:117-120 - a
+ * weighted gather-sum of stored unit fp32 rows of width 256.  M lists of m entries each, stride ld_list >= m elements: ids (int32 or
+ * int64, chosen by id_bytes = 4 or 8) and vals fp32.  part_rows: a device table of n_parts part base addresses (int64, as
+ * trid_p16_pack_multi_f32 takes its table; each the address of fp32 [part_len[s], 256] contiguous rows, 16-byte aligned); part_len: a
+ * second device table, int64 [n_parts], the parts' lengths in rows.  An entry id is read as row id & ((1 << shift) - 1) of part
+ * id >> shift; one index is the one-part case with shift = 0, which means id = local row of part 0 (n_parts must then be 1).  base:
+ * optional fp32 [M, 256] with stride ld_base elements (NULL: none).  For output row i and column c, every step rounded to fp32
+ * SEPARATELY - there is no contraction into an FMA:
+ *   acc = base ? base[i, c] : +0.0f
+ *   for j = 0 .. m-1, in list order:
+ *       id = ids[i, j]
+ *       if id < 0, or its part / row lies outside the tables' extents: skip (nothing is read through it)
+ *       t = fmaxf(vals[i, j], 0.0f)
+ *       w = (power == 0) ? 1.0f : t;  repeat (power - 1) times: w = w * t
+ *       acc = acc + (w * rows[id][c])          // one multiply, one add, always both - also when w == 0
+ *   out[i, c] = acc
+ * out fp32 [M, 256] contiguous; out aliases neither base nor a part.  0 <= power <= 4 (0: plain AQE / DBA averaging, >= 1: alpha-QE;
+ * the integer power is formed by repeated multiplication so that a numpy float32 restatement reproduces it exactly - powf is not
+ * called), 1 <= m <= 32.  A value that is negative, zero or -inf gives t = 0: weight 0 for power >= 1, weight 1 for power 0; NaN
+ * values and non-finite rows are undefined.  Argument errors (TRID_E_INVALID before any launch): a null table, ids, vals or out; m or
+ * power out of range; ld_list < m; id_bytes not 4 or 8; M < 1; shift outside [0, 31); n_parts < 1 (or != 1 with shift 0); base or
+ * out not 16-byte aligned, ld_base < 256 or not a multiple of 4; ids not id_bytes-aligned, vals not 4-byte, a table not 8-byte
+ * aligned.  Device contents are not validated and cannot fault as long as the tables are true: an id is used as an address only after
+ * 0 <= part < n_parts and 0 <= row < part_len[part] held.  One wave per output row (4 rows per workgroup of 256 threads), a lane
+ * owns 4 consecutive columns: one 16-byte load per gathered row per lane; the list entries are wave-uniform loads; 64-bit offsets; no
+ * LDS, no atomics.  Memory-bound: M * (m + 1) KB read, M KB written.  No host read, no allocation, one launch: it can be captured. */
+int trid_index_blend_rows_f32(const long long* part_rows, const long long* part_len, int n_parts, int shift, const void* ids,
+                              int id_bytes, const float* vals, long long ld_list, int M, int m, int power, const float* base,
+                              long long ld_base, float* out, void* stream);
 /* The merge step of GalleryIndex.refresh_neighbours (csrc/index_nn_update.hip): the stored neighbour lists nn [*, n] int32 and their
  * values nn_val [*, n] fp32 of the rows [0, rows) - value descending, then row ascending - take in m candidate rows numbered
  * cand_first .. cand_first + m - 1, rows <= cand_first: candidates are numbered above every merged row.  cand[j * ld_cand + i] = the

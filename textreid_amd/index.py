@@ -95,6 +95,22 @@ serial - the known limit.
     skips the pass and equals ``shortlist`` bit for bit.  G = 1e6, k = 100: 0.50 / 0.80 / 1.29 ms at Q = 1 / 8 / 32 against
     ``shortlist``'s 0.44 / 0.60 / 0.97 ms; the extra select is the cost, the bonus pass takes 0.01-0.05 ms.
 
+``expand_queries`` / ``search_expanded`` / ``search_expanded_pids`` and ``augmented`` are the other two post-processing steps of
+re-identification retrieval, query expansion (AQE; weighted: alpha-QE) and database-side augmentation (DBA), on the index itself
+(DESIGN.md section 7n).  Both are ONE kernel, ``trid_index_blend_rows_f32`` (csrc/index_blend.hip): a weighted gather-sum of stored
+unit fp32 rows, ``out[i] = base[i] + sum_j max(v_ij, 0) ** power * rows[id_ij]`` in list order, every multiply and add rounded to fp32
+on its own and the integer power (0 .. 4; 0 = plain averaging) formed by repeated multiplication - so a numpy float32 loop gives the
+same bits and the results are exact against a host restatement, like everything above.
+  * ``expand_queries(queries, m=5, power=1)``: per panel of 32 queries the two steps of ``shortlist`` with k = m (the m best ALLOWED
+    rows and their values), the blend with the unit query as base, ``trid_l2norm_rows_f32`` on the blend.  1 <= m <= ``MAX_EXPAND`` =
+    32; no mask: m <= live_count; with a mask nothing is read back and a query with fewer than m allowed rows blends what it has.
+  * ``search_expanded(queries, k, m, power)`` = ``shortlist(expand_queries(...), k, normalize=False, mask=mask)`` bit for bit (the same
+    allow set in both phases), without leaving the device or the cached buffers: no host read, capturable after one eager call.
+    ``search_expanded_pids`` selects through the two steps of ``shortlist_pids`` on the second pass.
+  * ``augmented(m=None, power=1)`` -> a NEW index whose every live row is the normalised blend of the first m entries of its own
+    neighbour list (weights from ``neighbour_values``; no base: the row leads its list), put through the ordinary ``add``; same
+    length, row numbers, pids and tombstones, no graph.  It needs a current graph with its values and leaves this index untouched.
+
 An index is used from ONE stream: ``add``, ``remove`` and ``search`` run on torch's current stream and share the cached workspace.
 A recorded search answers against the gallery as it stood at the capture (row count, storage, tombstones and neighbour graph are
 part of the recording): record again after ``add`` / ``remove`` / ``compact`` / ``build_neighbours`` / ``refresh_neighbours``.
@@ -105,7 +121,10 @@ private steps of ``_reranked`` below (``_rerank_plan``, ``_panel_scores``, ``_re
 Not built: widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
 or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
-pass); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits).
+pass); a graph build on the streaming filter kernel (its values only agree with the dense product to the last bits); a
+non-integer expansion power (``powf`` has no exact host restatement); ``augmented`` over ``GalleryShards`` and the expanded searches
+of its by-rank form (the rows of another rank are not addressable); an augmentation that keeps or rebuilds the graph (the new rows
+have other neighbours: ``build_neighbours`` on the result).
 """
 
 import torch
@@ -120,6 +139,8 @@ SMALL_Q = 32              # the panel width of trid_index_search_p16
 MAX_K = 16                # search / search_pids: the per-lane lists of the one-pass kernel
 MAX_SHORTLIST_K = MAX_DEEP_TOPK  # shortlist / search_reranked: the deep select over the dense score buffer (1024)
 MAX_NEIGHBOURS = 8        # build_neighbours: the list length of trid_index_rerank_add_f32 (and of trid_jaccard_add_f32)
+MAX_EXPAND = 32           # expand_queries / search_expanded: the list length of trid_index_blend_rows_f32
+MAX_EXPAND_POWER = 4      # ... and its largest integer power
 
 
 def _need_cuda(name, t):
@@ -937,6 +958,142 @@ class GalleryIndex:
         vals, rows = self._reranked("search_reranked_pids", queries, k, alpha, normalize, mask, distinct=True)
         pids = self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
         return vals, rows, pids
+
+    # ------------------------------------------------------------------ query expansion and database-side augmentation
+    def _blend_tables(self):
+        """-> (part addresses int64 [1], part lengths int64 [1]) on the device: this index as the ONE part of
+        trid_index_blend_rows_f32 (shift 0: id = local row).  Derived state like the mask words: rebuilt - one small upload, outside
+        any capture - when the storage or the length changed."""
+        key = (self._rows.data_ptr(), self._n)
+        if self._ws.get("blend_key") != key:
+            self._ws["blend_tab"] = torch.tensor(key, dtype=torch.int64, device=self._rows.device)
+            self._ws["blend_key"] = key
+        tab = self._ws["blend_tab"]
+        return tab[:1], tab[1:]
+
+    def _expand_buffers(self):
+        """the cached buffers of one expanded panel: the queries' own lists (fp32 values and int64 rows, 32 * MAX_EXPAND each), the
+        blend and the unit queries / the expanded queries ([32, 256] fp32 each) - allocated on first use, outside any capture"""
+        buf = self._ws.get("expand")
+        if buf is None:
+            dev = self._rows.device
+            buf = (torch.empty(SMALL_Q * MAX_EXPAND, dtype=torch.float32, device=dev), torch.empty(SMALL_Q * MAX_EXPAND, dtype=torch.int64, device=dev),
+                   torch.empty(SMALL_Q, self.dim, dtype=torch.float32, device=dev), torch.empty(SMALL_Q, self.dim, dtype=torch.float32, device=dev))
+            self._ws["expand"] = buf
+        return buf
+
+    def _check_expand(self, name, queries, k, m, power, mask, need_pids=False):
+        """the argument rules of expand_queries (k None) and the expanded searches: m and power (an empty index is told by the
+        shared rules), then those of shortlist -> the queries, fp32 contiguous"""
+        G = self._n
+        if G and (not isinstance(m, int) or m < 1 or m > MAX_EXPAND or m > G):
+            raise ValueError("GalleryIndex.%s: m must be in [1, %d] and <= len(index) = %d; got %r" % (name, MAX_EXPAND, G, m))
+        if G and mask is None and m > self.live_count:
+            raise ValueError("GalleryIndex.%s: m must be <= live_count = %d (%d of %d rows were removed); got %d" % (name, self.live_count, self._dead, G, m))
+        if not isinstance(power, int) or power < 0 or power > MAX_EXPAND_POWER:
+            raise ValueError("GalleryIndex.%s: power must be an integer in [0, %d]; got %r" % (name, MAX_EXPAND_POWER, power))
+        return self._check_search(name, queries, 1 if k is None else k, mask, need_pids=need_pids, max_k=MAX_SHORTLIST_K)
+
+    def _expanded(self, name, queries, k, m, power, normalize, mask, distinct=False):
+        """expand_queries (k None -> the expanded queries), search_expanded and search_expanded_pids (-> values, rows): one panel
+        loop.  Per panel of 32 queries: the dense product and the deep select with k = m over the allowed rows (shortlist's two
+        steps) = the queries' m best rows and their values; trid_index_blend_rows_f32 with the unit queries as base;
+        trid_l2norm_rows_f32 on the blend; then, for the searches, shortlist's steps again with the expanded queries (or the two
+        distinct-pid steps) and the SAME allow words."""
+        x = self._check_expand(name, queries, k, m, power, mask, need_pids=distinct)
+        Q, G, dev = x.shape[0], self._n, x.device
+        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        need = ops.L.load().trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0)
+        qval, qrow, blend, unit = self._expand_buffers()
+        tab, lens = self._blend_tables()
+        if k is None:
+            out = torch.empty(Q, self.dim, dtype=torch.float32, device=dev)
+            ws = self._deep_workspace(m)
+        else:
+            vals = torch.empty(Q, k, dtype=torch.float32, device=dev)
+            rows = torch.empty(Q, k, dtype=torch.int64, device=dev)
+            if distinct:
+                table, n_slots, best = self._distinct_setup(k)
+                ws = self._deep_workspace(m, slots=(n_slots, k))
+            else:
+                ws = self._deep_workspace(k, m)
+        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
+            part = x[at : at + SMALL_Q]
+            Qp = part.shape[0]
+            q16, _ = self._query_panel(part, normalize, need)
+            if normalize:
+                base = self._workspace(need)[1]  # (the normalised queries the panel was packed from)
+            else:
+                base = part if part.data_ptr() % 16 == 0 else unit[:Qp].copy_(part)  # (the blend reads 16 bytes per lane)
+            scores = self._dense_scores(q16)
+            qv, qr = qval[: Qp * m].view(Qp, m), qrow[: Qp * m].view(Qp, m)
+            _deep_topk(_p(scores), 1, scores.shape[1], Qp, G, m, words, qv, qr, ws=ws)
+            call("trid_index_blend_rows_f32", _p(tab), _p(lens), 1, 0, _p(qr), 8, _p(qv), m, Qp, m, power, _p(base), self.dim, _p(blend), stream())
+            new = out[at : at + Qp] if k is None else unit[:Qp]
+            call("trid_l2norm_rows_f32", _p(blend), _p(new), None, Qp, self.dim, 1e-12, stream())
+            if k is None:
+                continue
+            q16, _ = self._query_panel(new, False, need)
+            scores = self._dense_scores(q16)
+            if distinct:
+                self._distinct_select(scores, Qp, k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
+            else:
+                _deep_topk(_p(scores), 1, scores.shape[1], Qp, G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
+        return out if k is None else (vals, rows)
+
+    def expand_queries(self, queries, m=5, power=1, normalize=True, mask=None):
+        """-> unit fp32 [Q, 256]: query expansion (AQE for power = 0, its weighted form alpha-QE for power >= 1).  Every query is
+        replaced by the normalised weighted sum of itself and its m best allowed rows: with (v_j, r_j) the values and rows of
+        shortlist(queries, k=m, mask=mask), expanded = l2norm(unit query + sum_j max(v_j, 0) ** power * rows[r_j]), the sum taken in list order and
+        every multiply and add rounded to fp32 on its own (trid_index_blend_rows_f32, csrc/index_blend.hip; the power by repeated
+        multiplication), the norm by trid_l2norm_rows_f32 (eps 1e-12).  1 <= m <= MAX_EXPAND = 32, m <= len; without a mask
+        m <= live_count (ValueError); with a mask nothing is read back and a query with fewer than m allowed rows blends what it
+        has (-1 slots are skipped).  0 <= power <= 4.  queries, normalize, mask and the capture rule: as shortlist."""
+        return self._expanded("expand_queries", queries, None, m, power, normalize, mask)
+
+    def search_expanded(self, queries, k=10, m=5, power=1, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64): the exact k best allowed rows (1 <= k <= MAX_SHORTLIST_K = 1024) for the EXPANDED
+        queries - shortlist(expand_queries(queries, m, power, normalize, mask), k, normalize=False, mask=mask) bit for bit, the same
+        allow set in both phases - in panels of 32 queries through the cached score buffer and workspaces.  No host read; after one
+        eager call nothing is allocated but the outputs, so it can be captured with torch.cuda.graph: a replay reads the queries'
+        and the mask's contents at replay time; record again after add / remove / compact."""
+        return self._expanded("search_expanded", queries, k, m, power, normalize, mask)
+
+    def search_expanded_pids(self, queries, k=10, m=5, power=1, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64, pids [Q,k] i64): search_expanded over DISTINCT pids - the first phase is the same
+        (the m best allowed ROWS), the second pass selects through the two steps of shortlist_pids; it equals
+        shortlist_pids(expand_queries(...), k, normalize=False, mask=mask) bit for bit.  The index must hold pids."""
+        vals, rows = self._expanded("search_expanded_pids", queries, k, m, power, normalize, mask, distinct=True)
+        pids = self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
+        return vals, rows, pids
+
+    def augmented(self, m=None, power=1):
+        """-> a NEW GalleryIndex, database-side augmentation (DBA): every live row's embedding becomes the normalised weighted sum of
+        the first m entries of its own neighbour list - the row itself leads its list, so there is no base - with the weights
+        max(neighbour_values, 0) ** power (power 0: the plain mean direction): ONE trid_index_blend_rows_f32 launch over the lists
+        and their values, then the ordinary add (normalise, pack at the unit scale).  Same length, row numbers and pids; the same
+        rows are removed (their lists are all -1: a zero blend, and they are tombstones anyway); no graph.  This index is not
+        touched.  Needs a current graph whose values are held (RuntimeError naming build_neighbours / refresh_neighbours).  m
+        defaults to the graph's n; 1 <= m <= n; 0 <= power <= 4."""
+        if not self.neighbours_current or not self.neighbours_refreshable or self._n == 0:
+            raise RuntimeError("GalleryIndex.augmented: the neighbour graph is %s; call build_neighbours() (or refresh_neighbours()) first" % (
+                "absent" if self._nn is None else "held without its values" if self.neighbours_current else
+                "stale (add / remove / compact / load_state_dict since it was built)"))
+        n = self._nn.shape[1]
+        m = n if m is None else m
+        if not isinstance(m, int) or m < 1 or m > n:
+            raise ValueError("GalleryIndex.augmented: m must be in [1, n = %d] (the graph's list length); got %r" % (n, m))
+        if not isinstance(power, int) or power < 0 or power > MAX_EXPAND_POWER:
+            raise ValueError("GalleryIndex.augmented: power must be an integer in [0, %d]; got %r" % (MAX_EXPAND_POWER, power))
+        G = self._n
+        tab, lens = self._blend_tables()
+        blend = torch.empty(G, self.dim, dtype=torch.float32, device=self._rows.device)
+        call("trid_index_blend_rows_f32", _p(tab), _p(lens), 1, 0, _p(self._nn), 4, _p(self._nn_val), n, G, m, power, None, 0, _p(blend), stream())
+        new = GalleryIndex(capacity=G)
+        new.add(blend, self.pids)
+        if self._dead:
+            new.remove(rows=torch.nonzero(~self._live[:G]).reshape(-1))
+        return new
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):

@@ -70,6 +70,14 @@ concatenated rows has these lists (ids after the mapping), these values bit for 
     m = 0; the new rows' lists from the build's panel step; the flags of all parts read once on the host, flagged rows gathered
     32 at a time, recomputed by the panel step and scattered back.  Lists and values equal a fresh build bit for bit.
 
+Query expansion: ``expand_queries`` / ``search_expanded`` / ``search_expanded_pids`` with the signatures of the
+index and global row ids, in-process form only.  Phase 1 is the sharded ``shortlist`` with k = m; the blend is ONE launch of
+``trid_index_blend_rows_f32`` over the parts' fp32 row storages, through a device table of their addresses and lengths and
+``shift = 21`` (a global row decodes to its part and local row); ``trid_l2norm_rows_f32``; phase 2 is the sharded ``shortlist`` /
+``shortlist_pids`` with the same masks.  Equal to one index over the concatenated rows bit for bit.  By rank (``collective=True``) they
+raise a RuntimeError: the blend gathers rows by address and the rows of another rank are not addressable.  ``augmented()`` over
+shards is not built.
+
 Capture: in the in-process form, after one eager call a search reads nothing on the host and - while the candidates fit one merge
 launch - allocates nothing but its outputs: it can be recorded with ``torch.cuda.graph`` and replays against the current contents
 of the queries and masks (record again after ``add`` / ``remove``, as for the index).  ONE eager call before a capture is needed in
@@ -83,7 +91,7 @@ general, so it can be added), rebalancing rows between ranks, shards on several 
 import torch
 
 from . import ops, parallel
-from .index import DIM, MAX_K, MAX_NEIGHBOURS, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex
+from .index import DIM, MAX_EXPAND, MAX_EXPAND_POWER, MAX_K, MAX_NEIGHBOURS, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex
 from .ops import _p, call, stream
 
 SHARD_BITS = 21
@@ -376,6 +384,60 @@ class GalleryShards:
     def shortlist_pids(self, queries, k=100, normalize=True, mask=None):
         """-> (values, rows GLOBAL, pids), each [Q,k]: GalleryIndex.shortlist_pids over the shards, k <= 1024.  By-rank form: collective."""
         return self._search("shortlist_pids", queries, k, normalize, mask, MAX_SHORTLIST_K, True)
+
+    # ------------------------------------------------------------------ query expansion
+    def _blend_tables(self, dev):
+        """-> (part addresses int64 [S], part lengths int64 [S]) on the device: the parts' fp32 row storages as the address table of
+        trid_index_blend_rows_f32 (shift = SHARD_BITS: a global row decodes to its part and local row).  Cached; rebuilt - one small
+        upload, outside any capture - when a part's storage or length changed.  A part without storage has length 0."""
+        key = tuple((0, 0) if p._rows is None else (p._rows.data_ptr(), len(p)) for p in self._parts)
+        if self._ws.get("blend_key") != key:
+            self._ws["blend_tab"] = torch.tensor([[a for a, _ in key], [n for _, n in key]], dtype=torch.int64, device=dev)
+            self._ws["blend_key"] = key
+        tab = self._ws["blend_tab"]
+        return tab[0], tab[1]
+
+    def _expanded(self, name, queries, k, m, power, normalize, mask, distinct=False):
+        """expand_queries (k None) and the expanded searches, in-process form: phase 1 the sharded shortlist with k = m (global rows),
+        ONE blend launch over the parts' row storages with the unit queries as base, trid_l2norm_rows_f32, phase 2 the sharded
+        shortlist / shortlist_pids with the same masks"""
+        if self.collective:
+            raise RuntimeError("GalleryShards.%s: query expansion is not built for the by-rank form (collective=True): the blend gathers "
+                               "stored rows by address and the rows of another rank are not addressable" % name)
+        if not isinstance(m, int) or m < 1 or m > MAX_EXPAND:
+            raise ValueError("GalleryShards.%s: m must be in [1, %d]; got %r" % (name, MAX_EXPAND, m))
+        if not isinstance(power, int) or power < 0 or power > MAX_EXPAND_POWER:
+            raise ValueError("GalleryShards.%s: power must be an integer in [0, %d]; got %r" % (name, MAX_EXPAND_POWER, power))
+        x, _ = self._check(name, queries, 1 if k is None else k, mask, MAX_SHORTLIST_K, distinct)
+        if len(self) == 0:
+            raise ValueError("GalleryShards.%s: the shards are empty" % name)
+        Q = x.shape[0]
+        unit = ops.l2norm_rows(x)[0] if normalize else (x if x.data_ptr() % 16 == 0 else x.clone())
+        qv, qr = self._search("shortlist", unit, m, False, mask, MAX_SHORTLIST_K, False)
+        tab, lens = self._blend_tables(x.device)
+        blend = torch.empty(Q, DIM, dtype=torch.float32, device=x.device)
+        call("trid_index_blend_rows_f32", _p(tab), _p(lens), len(self._parts), SHARD_BITS, _p(qr), 8, _p(qv), m, Q, m, power, _p(unit), DIM,
+             _p(blend), stream())
+        new = ops.l2norm_rows(blend)[0]
+        if k is None:
+            return new
+        return self._search("shortlist_pids" if distinct else "shortlist", new, k, False, mask, MAX_SHORTLIST_K, distinct)
+
+    def expand_queries(self, queries, m=5, power=1, normalize=True, mask=None):
+        """-> unit fp32 [Q, 256]: GalleryIndex.expand_queries over the shards - every query replaced by the normalised weighted sum of
+        itself and its m best allowed rows of the WHOLE gallery (1 <= m <= 32, 0 <= power <= 4), bit for bit what one index over the
+        concatenated rows gives.  Like k, m is not checked against a row count: a query with fewer than m allowed rows blends what
+        it has.  In-process form only (by rank: RuntimeError)."""
+        return self._expanded("expand_queries", queries, None, m, power, normalize, mask)
+
+    def search_expanded(self, queries, k=10, m=5, power=1, normalize=True, mask=None):
+        """-> (values [Q,k] f32, rows [Q,k] i64 GLOBAL): GalleryIndex.search_expanded over the shards = shortlist(expand_queries(...), k,
+        normalize=False, mask=mask).  In-process form only (by rank: RuntimeError)."""
+        return self._expanded("search_expanded", queries, k, m, power, normalize, mask)
+
+    def search_expanded_pids(self, queries, k=10, m=5, power=1, normalize=True, mask=None):
+        """-> (values, rows GLOBAL, pids), each [Q,k]: GalleryIndex.search_expanded_pids over the shards.  In-process form only."""
+        return self._expanded("search_expanded_pids", queries, k, m, power, normalize, mask, distinct=True)
 
     # ------------------------------------------------------------------ neighbour graph over the shards
     def _sig(self):

@@ -7,7 +7,7 @@ Under torch.distributed.run with more than one rank --map times the SHARDED form
 positive_ranks_sharded: the same synthetic gallery split evenly over the ranks, queries replicated, one rank per device when the box has
 them) and rank 0 prints one JSON line with world, map_rows_per_s and map_rerank_rows_per_s (GLOBAL gallery rows per second).
 usage: python -m torch.distributed.run --nproc_per_node W tools/retrieval_time.py [G] [Q] --map
-usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]]
+usage: python tools/retrieval_time.py --index [G] [Q ...] [--wg N] [--masked [F]] [--distinct [M]] [--deep K [K ...]] [--rerank K [K ...]] [--expanded M [M ...]]
                                        [--deep-distinct ROWS_PER_PID K [K ...]] [--shards S [--shards-rerank] [--shards-refresh M [M ...]]]
 --index: small-batch serving.  For each Q (default 1 8 32 64 256; G default 1e6) three forms are timed in one process, alternating,
 after 3 warm-up calls each, over 20 calls that each end in a synchronise: GalleryIndex.search, similarity_topk(q, g, 10) on raw
@@ -36,6 +36,11 @@ median of shortlist_pids and the time of the group-best pass alone.
 same index for each K, timed in the same process alternating with the others.  Each Q entry gains reranked_ms and reranked_shortlist_ms
 {K: median, min, max}, reranked_over_shortlist {K: ratio of the medians}, reranked_split_ms {K: {entry point: ms}} (the bonus pass is
 trid_index_rerank_add_f32) and bonus_floor_ms: the graph's G * n * 4 bytes read once per panel of 32 queries, at 6.3 TB/s.
+--expanded M [M ...]: GalleryIndex.search_expanded(k = 100, m = M, power = 1) for each M next to shortlist(k = 100) of the same index - the
+yardstick - timed in the same process alternating with the others.  Each Q entry gains expanded_ms {M: median, min, max},
+expanded_shortlist_ms, expanded_over_shortlist {M: ratio of the medians}, expanded_split_ms {M: {entry point: ms}} (the blend is
+trid_index_blend_rows_f32), blend_floor_ms {M: Q * (M + 2) KB at 6.3 TB/s} and expanded_equals_composition {M: search_expanded ==
+shortlist(expand_queries(...)) bit for bit}.
 --refresh M [M ...]: after the Q loop and a timed build_neighbours(5) (the one of --rerank if given), per M: M rows are appended and
 GalleryIndex.refresh_neighbours() is timed (add_refresh_ms, add_counts = what it returned), then M random live rows are removed and it is
 timed again (remove_refresh_ms, remove_counts) - each one call after one untimed warm-up refresh of either kind; each change is then made
@@ -100,6 +105,14 @@ def index_main(argv):
             rerank.append(int(argv[j]))
             j += 1
         argv = argv[:i] + argv[j:]
+    expanded = []
+    if "--expanded" in argv:  # (as --deep: every bare number after it is an M)
+        i = argv.index("--expanded")
+        j = i + 1
+        while j < len(argv) and not argv[j].startswith("--"):
+            expanded.append(int(argv[j]))
+            j += 1
+        argv = argv[:i] + argv[j:]
     refresh = []
     if "--refresh" in argv:  # (as --deep: every bare number after it is an M)
         i = argv.index("--refresh")
@@ -133,6 +146,7 @@ def index_main(argv):
     G = nums[0] if nums else 1000000
     Qs = nums[1:] if len(nums) > 1 else [1, 8, 32, 64, 256]
     CALLS, WARM, K, HBM = 20, 3, 10, 6.3e12
+    KE = 100  # the depth --expanded times search_expanded and its yardstick shortlist at
     gen = torch.Generator(device="cpu").manual_seed(7)
     g_raw = (torch.randn(G, 256, generator=gen) * 3.0).cuda()
     idx = GalleryIndex(capacity=G + 2 * sum(refresh) + (1 if refresh else 0))  # (--refresh appends 2 M rows per M: no growth inside the measurement)
@@ -237,6 +251,10 @@ def index_main(argv):
         for kr in rerank:
             forms["shortlist_k%d" % kr] = lambda kr=kr: idx.shortlist(q_raw, kr)
             forms["reranked_k%d" % kr] = lambda kr=kr: idx.search_reranked(q_raw, kr)
+        if expanded:
+            forms["expanded_shortlist"] = lambda: idx.shortlist(q_raw, KE)
+        for me in expanded:
+            forms["expanded_m%d" % me] = lambda me=me: idx.search_expanded(q_raw, KE, m=me)
         for name, ks in (SHARD_FORMS if shards else ()):
             forms["shards_plain_%s" % name] = lambda name=name, ks=ks: getattr(idx_s, name)(q_raw, ks)
             forms["shards_%s" % name] = lambda name=name, ks=ks: getattr(sh, name)(q_raw, ks)
@@ -269,6 +287,17 @@ def index_main(argv):
                 a, b = getattr(sh, name)(q_raw, ks), getattr(idx_s, name if Q <= 32 or name != "search" else "shortlist")(q_raw, ks)
                 rows = (b[1] // shard_rows) * SHARD_STRIDE + b[1] % shard_rows
                 ent["shards_equal_plain"][name] = bool(torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], rows))
+        if expanded:  # the blend reads Q * (m + 1) KB and writes Q KB
+            ent["expanded_k"] = KE
+            ent["expanded_shortlist_ms"] = ent.pop("expanded_shortlist_ms")
+            ent["expanded_ms"] = {str(me): ent.pop("expanded_m%d_ms" % me) for me in expanded}
+            ent["expanded_over_shortlist"] = {str(me): ent["expanded_ms"][str(me)]["median"] / ent["expanded_shortlist_ms"]["median"] for me in expanded}
+            ent["expanded_split_ms"] = {str(me): split_of(lambda me=me: idx.search_expanded(q_raw, KE, m=me)) for me in expanded}
+            ent["blend_floor_ms"] = {str(me): Q * (me + 2) * 1024 / HBM * 1e3 for me in expanded}
+            ent["expanded_equals_composition"] = {}
+            for me in expanded:
+                a, b = idx.search_expanded(q_raw, KE, m=me), idx.shortlist(idx.expand_queries(q_raw, m=me), KE, normalize=False)
+                ent["expanded_equals_composition"][str(me)] = bool(torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1]))
         if idx_m is not None:
             ent["masked_over_index"] = ent["index_masked_ms"]["median"] / ent["index_ms"]["median"]
             ent["masked_within_index_spread"] = bool(ent["index_ms"]["min"] <= ent["index_masked_ms"]["median"] <= ent["index_ms"]["max"])
