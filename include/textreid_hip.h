@@ -925,7 +925,7 @@ int trid_index_blend_rows_f32(const long long* part_rows, const long long* part_
  * ld_cand >= rows when m > 0, cand / nn / nn_val 4-byte aligned.  No host read, no allocation, one launch. */
 int trid_index_nn_merge_f32(const float* cand, long long ld_cand, int m, int cand_first, int rows, const uint8_t* live, int32_t* nn,
                             float* nn_val, int n, uint8_t* redo, void* stream);
-/* The merge step of GalleryShards.refresh_neighbours (csrc/index_shard_graph.hip): the merge above for lists of GLOBAL row ids,
+/* The merge step of GalleryShards.refresh_neighbours (csrc/index_nn_update.hip, the same kernel body with the sharded liveness policy): the merge above for lists of GLOBAL row ids,
  * id = shard * 2^21 + local row, of the rows [0, rows) of shard self_shard.  Two differences:
  *   (a) liveness by global id.  live_all uint8 [live_bytes]: the shards' liveness bytes concatenated; shard s owns
  *       live_all[live_off[s] .. live_off[s] + live_len[s]) (live_off int64 [n_shards], live_len int32 [n_shards], both on the device).

@@ -117,7 +117,14 @@ part of the recording): record again after ``add`` / ``remove`` / ``compact`` / 
 
 More than ``MAX_ROWS`` rows, or one part per rank: ``GalleryShards`` (textreid_amd/index_shards.py) composes
 plain indexes and merges their lists exactly; its neighbour graph over all shards and its re-ranked searches (section 7m) run the
-private steps of ``_reranked`` below (``_rerank_plan``, ``_panel_scores``, ``_rerank_own_lists``, ``_rerank_bonus``, ``_rerank_select``).
+private steps of this module.  The whole set it touches: the module helpers ``_need_cuda``, ``_graph_pair``, ``_blank_dead`` and
+``_fill_panel``; of a part, the steps of the deep panel loop (``_search_plan``, ``_panel_scores``, ``_rerank_own_lists``,
+``_rerank_bonus``, ``_rerank_select``), the one-pass dispatcher and its workspace (``_one_pass``, ``_neighbour_workspace``),
+``_candidate_scores``, ``_pids_of`` and the field ``_has_pids``.  Everything else goes through the public faces.
+
+Inside the class every step is written once: ``_allow_words`` (the allow words of a call), ``_pids_of``, ``_outputs``, ``_one_pass`` (the
+only caller of the three one-pass entry points), ``_search_plan`` (what the panels of a deep search share) and ``_deep_panels`` (the
+one panel loop of ``shortlist``, ``shortlist_pids``, the re-ranked and the expanded searches: product, optional middle step, select).
 Not built: widths other than 256, in-place re-embedding of a row, an
 image-encoder convenience wrapper (``add`` takes embeddings, e.g. the image half of ``inference`` output); a refresh that ``add``
 or ``remove`` runs by itself (they make the graph stale; the caller decides when ``refresh_neighbours`` is worth its gallery
@@ -143,9 +150,46 @@ MAX_EXPAND = 32           # expand_queries / search_expanded: the list length of
 MAX_EXPAND_POWER = 4      # ... and its largest integer power
 
 
-def _need_cuda(name, t):
+def _need_cuda(name, t, owner="index.GalleryIndex"):
     if not t.is_cuda:
-        raise RuntimeError("textreid_amd.index.GalleryIndex.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
+        raise RuntimeError("textreid_amd.%s.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % (owner, name))
+
+
+def _graph_pair(cap, n, device, values=True, old=None, rows=0):
+    """-> (lists int32 [cap, n] filled with -1, values fp32 [cap, n] filled with -inf, or None without ``values``): the storage of a
+    neighbour graph.  ``old`` = (lists, values or None): its first ``rows`` rows are carried over, and values are held iff it held them."""
+    if old is not None:
+        values = old[1] is not None
+    nn = torch.full((cap, n), -1, dtype=torch.int32, device=device)
+    val = torch.full((cap, n), float("-inf"), dtype=torch.float32, device=device) if values else None
+    if old is not None and rows:
+        nn[:rows].copy_(old[0][:rows])
+        if values:
+            val[:rows].copy_(old[1][:rows])
+    return nn, val
+
+
+def _blank_dead(nn, val, live):
+    """(-1, -inf) into every slot of the rows that are not live: lists, values (or None) and liveness of the SAME row range"""
+    dead = ~live[:, None]
+    nn.masked_fill_(dead, -1)
+    if val is not None:
+        val.masked_fill_(dead, float("-inf"))
+
+
+def _fill_panel(q16, src, Q, held):
+    """the Q P16 rows ``src`` into a zero-padded [32, 256] panel whose first ``held`` rows were written before (bit copies: the rows
+    carry the fixed unit scale) -> the rows it holds now, Q"""
+    q16.view(torch.int32)[:Q].copy_(src.view(torch.int32))
+    if Q < held:
+        q16[Q:held].zero_()
+    return Q
+
+
+def _panel_of(at, Q, *tensors):
+    """the rows [at, at + 32) of tensors that hold Q rows (None stays None) - the tensors themselves when they are ONE panel: the
+    latency path makes no views"""
+    return tensors if Q <= SMALL_Q else tuple(None if t is None else t[at : at + SMALL_Q] for t in tensors)
 
 
 def group_ids(pids):
@@ -291,13 +335,7 @@ class GalleryIndex:
         self._rows, self._p16, self._pids, self._live = rows, p16, pids, live
         self._words_ok = self._gids_ok = self._gtab_ok = False
         if self._nn is not None:  # (the lists grow with the storage like the other workspaces; growth alone changes nothing in them)
-            nn = torch.full((new_cap, self._nn.shape[1]), -1, dtype=torch.int32, device=device)
-            nn[: self._n].copy_(self._nn[: self._n])
-            self._nn = nn
-            if self._nn_val is not None:
-                val = torch.full((new_cap, self._nn_val.shape[1]), float("-inf"), dtype=torch.float32, device=device)
-                val[: self._n].copy_(self._nn_val[: self._n])
-                self._nn_val = val
+            self._nn, self._nn_val = _graph_pair(new_cap, self._nn.shape[1], device, old=(self._nn, self._nn_val), rows=self._n)
         if self._unit is None:
             self._unit = torch.ones(1, dtype=torch.float32, device=device)
 
@@ -416,14 +454,11 @@ class GalleryIndex:
         self._live = torch.ones(cap, dtype=torch.bool, device=dev)
         self._n, self._dead, self._words_ok, self._gids_ok, self._gtab_ok = m, 0, False, False, False
         if keep_neighbours and self.neighbours_current and m:
-            nn = torch.full((cap, self._nn.shape[1]), -1, dtype=torch.int32, device=dev)
+            nn, val = _graph_pair(cap, self._nn.shape[1], dev, values=self._nn_val is not None)
             nn[:m] = new_of[self._nn[keep].long()].int()
-            self._nn = nn
-            if self._nn_val is not None:
-                val = torch.full((cap, self._nn_val.shape[1]), float("-inf"), dtype=torch.float32, device=dev)
+            if val is not None:
                 val[:m] = self._nn_val[keep]
-                self._nn_val = val
-            self._nn_rows = m
+            self._nn, self._nn_val, self._nn_rows = nn, val, m
         else:
             self._nn, self._nn_val, self._nn_ok, self._nn_rows = None, None, False, 0  # (the lists hold the old row numbers: dropped, not kept as a trap)
         if m == 0:
@@ -501,21 +536,43 @@ class GalleryIndex:
         call("trid_p16_pack_f32", _p(x), Q, self.dim, self.dim, _p(self._unit), _p(q16), 1, stream())
         return q16, lists
 
+    def _one_pass(self, panel, Q, k, vals, rows, lists, words=None, gids=None, workgroups=0):
+        """THE dispatcher of the one-pass kernel: the Q <= 32 rows of the P16 panel at ``panel`` as the queries against the whole P16
+        gallery -> vals fp32 / rows int64 [Q, k].  lists: the kernel's list workspace (_query_panel, _neighbour_workspace).  words:
+        the packed allow bits (the masked kernel); None: every row may be returned.  gids: the rows' group ids (the distinct kernel:
+        at most one row per group)."""
+        G = self._n
+        if gids is not None:
+            call("trid_index_search_distinct_p16", _p(panel), _p(self._p16), _p(self._unit), _p(gids), None if words is None else _p(words), Q, G, k, 0,
+                 _p(vals), _p(rows), _p(lists), workgroups, stream())
+        elif words is None:
+            call("trid_index_search_p16", _p(panel), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+        else:
+            call("trid_index_search_masked_p16", _p(panel), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+
     def _search_small(self, x, k, normalize, vals, rows, workgroups=0, words=None, gids=None):
-        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery.  No host read.
-        words: the packed allow bits (the masked kernel); None: every row may be returned.  gids: the rows' group ids (the
-        distinct kernel: at most one row per group)."""
+        """Q <= 32: normalise into the cached buffer, pack with the unit scalar, ONE pass over the P16 gallery (_one_pass).  No host read."""
         Q, G = x.shape[0], self._n
         L = ops.L.load()
         need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, Q, k, workgroups))
         q16, lists = self._query_panel(x, normalize, need)
-        if gids is not None:
-            call("trid_index_search_distinct_p16", _p(q16), _p(self._p16), _p(self._unit), _p(gids), None if words is None else _p(words), Q, G, k, 0,
-                 _p(vals), _p(rows), _p(lists), workgroups, stream())
-        elif words is None:
-            call("trid_index_search_p16", _p(q16), _p(self._p16), _p(self._unit), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
-        else:
-            call("trid_index_search_masked_p16", _p(q16), _p(self._p16), _p(self._unit), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(lists), workgroups, stream())
+        self._one_pass(q16, Q, k, vals, rows, lists, words, gids, workgroups)
+
+    def _allow_words(self, mask, extent=0):
+        """the allow words of one call: those of ``live & mask`` (_mask_words), or None when every row is allowed - no mask, no
+        tombstones, and no ``extent`` beyond len (rows the caller walks behind len: their bits are zero)"""
+        if mask is None and not self._dead and extent <= self._n:
+            return None
+        return self._mask_words(None if mask is None else mask.contiguous())
+
+    def _pids_of(self, rows):
+        """rows int64 (local, -1 in short slots) -> their pids, -1 in short slots (a -1 indexes the last row: in range, then overwritten)"""
+        return self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
+
+    @staticmethod
+    def _outputs(Q, k, device):
+        """-> (values fp32 [Q, k], rows int64 [Q, k]): the only allocation of a search in steady state"""
+        return torch.empty(Q, k, dtype=torch.float32, device=device), torch.empty(Q, k, dtype=torch.int64, device=device)
 
     def _check_search(self, name, queries, k, mask, need_pids=False, max_k=MAX_K, need_graph=False):
         """the argument rules search, search_pids, shortlist, shortlist_pids and the re-ranked searches share, in the order the messages are promised -> the
@@ -560,18 +617,12 @@ class GalleryIndex:
         k <= live_count.  With a mask: a query with fewer than k allowed rows ends in (-inf, -1) slots."""
         x = self._check_search("search", queries, k, mask)
         Q, G = x.shape[0], self._n
-        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
-        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        if mask is not None or self._dead:
-            words = self._mask_words(None if mask is None else mask.contiguous())
-            if Q <= SMALL_Q:
-                self._search_small(x, k, normalize, vals, rows, words=words)
-                return vals, rows
+        vals, rows = self._outputs(Q, k, x.device)
+        words = self._allow_words(mask)
+        if words is not None or Q <= SMALL_Q:
             for at in range(0, Q, SMALL_Q):  # panels of 32 queries, one gallery pass each, into slices of the outputs
-                self._search_small(x[at : at + SMALL_Q], k, normalize, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], words=words)
-            return vals, rows
-        if Q <= SMALL_Q:
-            self._search_small(x, k, normalize, vals, rows)
+                part, pv, pr = _panel_of(at, Q, x, vals, rows)
+                self._search_small(part, k, normalize, pv, pr, words=words)
             return vals, rows
         q = ops.l2norm_rows(x)[0] if normalize else x
         return _Operands(q, self._rows[:G], ga=self._unit, g16=self._p16[:G]).topk(k, out=(vals, rows))
@@ -584,15 +635,14 @@ class GalleryIndex:
         again after add / remove / compact.  queries, k, normalize, mask: as search (no mask: k <= live_count).  The index must
         hold pids.  A query with fewer than k distinct allowed pids ends in (-inf, -1, -1) slots."""
         x = self._check_search("search_pids", queries, k, mask, need_pids=True)
-        Q, G = x.shape[0], self._n
-        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
-        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
+        Q = x.shape[0]
+        vals, rows = self._outputs(Q, k, x.device)
+        words = self._allow_words(mask)
         gids = self._group_ids()
         for at in range(0, Q, SMALL_Q):  # panels of 32 queries, one gallery pass each, into slices of the outputs
-            self._search_small(x[at : at + SMALL_Q], k, normalize, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], words=words, gids=gids)
-        pids = self._pids[:G][rows].masked_fill_(rows < 0, -1)  # (a short slot's -1 indexes the last row: in range, then overwritten)
-        return vals, rows, pids
+            part, pv, pr = _panel_of(at, Q, x, vals, rows)
+            self._search_small(part, k, normalize, pv, pr, words=words, gids=gids)
+        return vals, rows, self._pids_of(rows)
 
     # ------------------------------------------------------------------ shortlist
     def _score_buffer(self, cols):
@@ -649,19 +699,7 @@ class GalleryIndex:
         with fewer than k allowed rows ends in (-inf, -1) slots).  No host read; after one eager call (which builds the score
         buffer and the workspaces) nothing is allocated but the outputs, so it can be captured with torch.cuda.graph: a replay
         reads the queries' and the mask's contents at replay time; record again after add / remove / compact."""
-        x = self._check_search("shortlist", queries, k, mask, max_k=MAX_SHORTLIST_K)
-        Q, G = x.shape[0], self._n
-        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
-        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
-        L = ops.L.load()
-        ws = self._deep_workspace(k)
-        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
-            part = x[at : at + SMALL_Q]
-            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
-            scores = self._dense_scores(q16)
-            _deep_topk(_p(scores), 1, scores.shape[1], part.shape[0], G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
-        return vals, rows
+        return self._reranked("shortlist", queries, k, None, normalize, mask, distinct=False)
 
     # ------------------------------------------------------------------ deep distinct search
     def _group_table(self):
@@ -713,21 +751,8 @@ class GalleryIndex:
         group table - one read of the group count - the buffers and the workspaces) nothing is allocated but the outputs, so it can
         be captured with torch.cuda.graph: a replay reads the queries' and the mask's contents at replay time; record again after
         add / remove / compact.  One wave walks a pid's rows: a pid holding most of the gallery is serial."""
-        x = self._check_search("shortlist_pids", queries, k, mask, need_pids=True, max_k=MAX_SHORTLIST_K)
-        Q, G = x.shape[0], self._n
-        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
-        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
-        L = ops.L.load()
-        table, n_slots, best = self._distinct_setup(k)
-        ws = self._deep_workspace(slots=(n_slots, k))
-        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
-            part = x[at : at + SMALL_Q]
-            q16, _ = self._query_panel(part, normalize, L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0))
-            scores = self._dense_scores(q16)
-            self._distinct_select(scores, part.shape[0], k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
-        pids = self._pids[:G][rows].masked_fill_(rows < 0, -1)  # (a short slot's -1 indexes the last row: in range, then overwritten)
-        return vals, rows, pids
+        vals, rows = self._reranked("shortlist_pids", queries, k, None, normalize, mask, distinct=True)
+        return vals, rows, self._pids_of(rows)
 
     # ------------------------------------------------------------------ neighbour graph and re-ranked search
     def build_neighbours(self, n=5):
@@ -746,28 +771,13 @@ class GalleryIndex:
             raise ValueError("GalleryIndex.build_neighbours: the index is empty")
         if n > self.live_count:
             raise ValueError("GalleryIndex.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
-        dev = self._rows.device
         found, vals = self._neighbour_panels(0, G, n)
-        if self._nn is None or self._nn.shape[1] != n or self._nn.shape[0] < self.capacity:
-            self._nn = torch.empty(self.capacity, n, dtype=torch.int32, device=dev)
-        if self._nn_val is None or self._nn_val.shape != self._nn.shape:
-            self._nn_val = torch.empty(self.capacity, n, dtype=torch.float32, device=dev)
+        self._nn, self._nn_val = _graph_pair(self.capacity, n, self._rows.device)
         self._nn[:G].copy_(found)
-        self._nn[G:] = -1
         self._nn_val[:G].copy_(vals)
-        self._nn_val[G:] = float("-inf")
         if self._dead:
-            self._nn[:G].masked_fill_(~self._live[:G, None], -1)
-            self._nn_val[:G].masked_fill_(~self._live[:G, None], float("-inf"))
+            _blank_dead(self._nn[:G], self._nn_val[:G], self._live[:G])
         self._nn_ok, self._nn_rows = True, G
-
-    def _neighbour_search(self, panel, Q, n, words, lists, vals, found):
-        """one pass of the one-pass kernel with k = n: the Q rows of ``panel`` as the queries against the whole P16 gallery"""
-        G = self._n
-        if words is None:
-            call("trid_index_search_p16", _p(panel), _p(self._p16), _p(self._unit), Q, G, n, 0, _p(vals), _p(found), _p(lists), 0, stream())
-        else:
-            call("trid_index_search_masked_p16", _p(panel), _p(self._p16), _p(self._unit), _p(words), Q, G, n, 0, _p(vals), _p(found), _p(lists), 0, stream())
 
     def _neighbour_workspace(self, n):
         """-> (the cached zero-padded panel, the kernel's list workspace, the tombstone words or None) for neighbour searches at k = n
@@ -776,13 +786,6 @@ class GalleryIndex:
         need = max(L.trid_index_search_ws_bytes(self._n, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(self._n, SMALL_Q, n, 0))
         q16, _, _, lists = self._workspace(need)  # (workers x Q x k x 8 bytes: the full panel covers every smaller one)
         return q16, lists, (self._mask_words(None) if self._dead else None)
-
-    def _fill_panel(self, q16, src, Q):
-        """the Q P16 rows ``src`` into the cached zero-padded panel (bit copies: they carry the fixed unit scale)"""
-        q16.view(torch.int32)[:Q].copy_(src.view(torch.int32))
-        if Q < self._panel_rows:
-            q16[Q : self._panel_rows].zero_()
-        self._panel_rows = Q
 
     def _neighbour_panels(self, first, last, n):
         """the panel loop of build_neighbours over the rows [first, last) -> (found int64 [last - first, n], vals fp32 [same]): panels
@@ -798,18 +801,20 @@ class GalleryIndex:
             if Q == SMALL_Q:  # (the stored rows ARE a panel: packed with the unit scalar, 1024 bytes per row, 16-byte aligned)
                 panel = self._p16[at : at + SMALL_Q]
             else:
-                self._fill_panel(q16, self._p16[at : at + Q], Q)
+                self._panel_rows = _fill_panel(q16, self._p16[at : at + Q], Q, self._panel_rows)
                 panel = q16
-            self._neighbour_search(panel, Q, n, words, lists, vals[at - first :], found[at - first :])
+            self._one_pass(panel, Q, n, vals[at - first :], found[at - first :], lists, words)
         return found, vals
 
-    def _candidate_scores(self, at, m, n0):
+    def _candidate_scores(self, at, m, n0, src=None):
         """-> the cached score buffer holding, as a row-major [m, n0] matrix at its start, the similarity of every old row i < n0 AS THE
-        QUERY to the m <= 32 rows from ``at``: trid_gemm_p16 with the m P16 rows as A (gallery role) and the P16 rows [0, n0) as B
+        QUERY to the m <= 32 rows from ``at`` of ``src`` (another index: a part of GalleryShards; default: this one): trid_gemm_p16
+        with the m P16 rows as A (gallery role) and the P16 rows [0, n0) as B
         (query role), both at the unit scale - the operand roles of the build's products, so the same fp32 numbers (DESIGN.md section
         7j).  Always the tile kernel: the streaming short-K kernel ops.gemm_p16 would pick for n0 % 32 == 0 sums in another order."""
+        src = self if src is None else src
         cand = self._score_buffer(self._ws.get("cols", SMALL_Q))  # (capacity * cols >= 32 * n0 floats)
-        ops.gemm_p16(ops.P16(self._p16[at : at + m], self._unit), ops.P16(self._p16[:n0], self._unit), cand, m, n0, self.dim, n0, tile_only=True)
+        ops.gemm_p16(ops.P16(src._p16[at : at + m], src._unit), ops.P16(self._p16[:n0], self._unit), cand, m, n0, self.dim, n0, tile_only=True)
         return cand
 
     def refresh_neighbours(self):
@@ -855,9 +860,7 @@ class GalleryIndex:
             found, vals = self._neighbour_panels(n0, n1, n)
             self._nn[n0:n1].copy_(found)
             self._nn_val[n0:n1].copy_(vals)
-            dead = ~self._live[n0:n1, None]
-            self._nn[n0:n1].masked_fill_(dead, -1)
-            self._nn_val[n0:n1].masked_fill_(dead, float("-inf"))
+            _blank_dead(self._nn[n0:n1], self._nn_val[n0:n1], self._live[n0:n1])
         again = torch.nonzero(redo).reshape(-1)  # (the one host read: how many rows, and which)
         if again.numel():
             q16, lists, words = self._neighbour_workspace(n)
@@ -866,8 +869,8 @@ class GalleryIndex:
             for at in range(0, again.numel(), SMALL_Q):
                 rows = again[at : at + SMALL_Q]
                 Q = rows.numel()
-                self._fill_panel(q16, self._p16.view(torch.int32)[rows], Q)
-                self._neighbour_search(q16, Q, n, words, lists, vals, found)
+                self._panel_rows = _fill_panel(q16, self._p16.view(torch.int32)[rows], Q, self._panel_rows)
+                self._one_pass(q16, Q, n, vals, found, lists, words)
                 self._nn[rows] = found[:Q].int()
                 self._nn_val[rows] = vals[:Q]
         new_rows = int(self._live[n0:n1].sum()) if n1 > n0 else 0
@@ -888,40 +891,55 @@ class GalleryIndex:
         return self._reranked("search_reranked", queries, k, alpha, normalize, mask, distinct=False)
 
     def _reranked(self, name, queries, k, alpha, normalize, mask, distinct):
-        """search_reranked (distinct=False) and search_reranked_pids (True) -> (values, rows): one panel loop, the product, the
-        query's own list and the bonus pass are shared; the final select is the deep row select or the two steps of shortlist_pids"""
-        x = self._check_search(name, queries, k, mask, need_pids=distinct, max_k=MAX_SHORTLIST_K, need_graph=True)
-        alpha = float(alpha)
-        Q, n = x.shape[0], self._nn.shape[1]
-        vals = torch.empty(Q, k, dtype=torch.float32, device=x.device)
-        rows = torch.empty(Q, k, dtype=torch.int64, device=x.device)
-        plan = self._rerank_plan(k, n, mask, distinct)
-        if alpha != 0.0:
-            qnn = torch.empty(min(Q, SMALL_Q), n, dtype=torch.int64, device=x.device)
-            qval = torch.empty(min(Q, SMALL_Q), n, dtype=torch.float32, device=x.device)
-        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
-            part = x[at : at + SMALL_Q]
-            scores = self._panel_scores(part, normalize)
-            if alpha != 0.0:
-                self._rerank_own_lists(plan, scores, part.shape[0], n, qval, qnn)
-                self._rerank_bonus(plan, scores, part.shape[0], qnn, self._nn, n, alpha)
-            self._rerank_select(plan, scores, part.shape[0], k, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
-        return vals, rows
+        """the shortlists (alpha None: no graph is asked for) and the re-ranked searches, over rows (distinct=False) or distinct pids
+        (True) -> (values, rows): the panel loop with, for alpha != 0, the query's own list and the bonus pass as its middle step"""
+        graph = alpha is not None
+        x = self._check_search(name, queries, k, mask, need_pids=distinct, max_k=MAX_SHORTLIST_K, need_graph=graph)
+        alpha = float(alpha) if graph else 0.0
+        plan = self._search_plan(k, mask, distinct, also=(self._nn.shape[1],) if graph else ())
+        if alpha == 0.0:  # (no bonus, and no select that only feeds it)
+            return self._deep_panels(x, k, normalize, plan)
+        n, Qp = self._nn.shape[1], min(x.shape[0], SMALL_Q)
+        qnn = torch.empty(Qp, n, dtype=torch.int64, device=x.device)
+        qval = torch.empty(Qp, n, dtype=torch.float32, device=x.device)
 
-    # the private steps of a re-ranked search: _reranked above runs them on one index, GalleryShards (index_shards.py) runs them in two
-    # phases over its parts with the merge of the parts' lists between them.
-    def _rerank_plan(self, k, n, mask, distinct, extent=0):
-        """what every panel of one re-ranked search shares -> (G, words, ws, distinct state or None).  G = the rows the selects and the
+        def bonus(at, part, scores):
+            self._rerank_own_lists(plan, scores, part.shape[0], n, qval, qnn)
+            self._rerank_bonus(plan, scores, part.shape[0], qnn, self._nn, n, alpha)
+            return scores
+
+        return self._deep_panels(x, k, normalize, plan, bonus)
+
+    # the private steps of a deep search: _deep_panels runs them on one index, GalleryShards (index_shards.py) runs them in two phases
+    # over its parts with the merge of the parts' lists between them.
+    def _search_plan(self, k, mask, distinct=False, also=(), extent=0):
+        """what every panel of one deep search shares -> (G, words, ws, distinct state or None).  G = the rows the selects and the
         bonus pass walk: len, or ``extent`` when that is more (GalleryShards: a part with fewer rows than the graph's n is walked as
         ``extent`` = n rows, the extra ones masked off - the allow words are then always given, and they are zero behind len).
-        words: the allow words of ``live & mask``, None when every row is allowed; ws: the deep select's workspace for k and n over
-        G rows (and the pairs select of the distinct form)."""
+        words: the allow words of the call (_allow_words); ws: the deep select's workspace over G rows for the final select - k
+        (None: no final select), or the pairs select of the distinct form - and for every other k in ``also`` (the graph's n, the
+        expansion's m)."""
         G = max(self._n, extent)
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead or G > self._n) else None
+        words = self._allow_words(mask, extent)
         if distinct:
             table, n_slots, best = self._distinct_setup(k)
-            return G, words, self._deep_workspace(n, slots=(n_slots, k), rows=G), (table, n_slots, best)
-        return G, words, self._deep_workspace(k, n, rows=G), None
+            return G, words, self._deep_workspace(*also, slots=(n_slots, k), rows=G), (table, n_slots, best)
+        return G, words, self._deep_workspace(*([] if k is None else [k]), *also, rows=G), None
+
+    def _deep_panels(self, x, k, normalize, plan, middle=None):
+        """THE panel loop of the deep searches -> (values [Q, k], rows [Q, k]): per panel of 32 queries the dense product into the one
+        score buffer (_panel_scores), the optional ``middle(at, part, scores)`` -> the buffer to select from (None: this panel is
+        done), the final select (_rerank_select) into slices of the outputs.  k None: no outputs, the middle step keeps what it makes."""
+        Q = x.shape[0]
+        vals, rows = self._outputs(Q, k, x.device) if k is not None else (None, None)
+        for at in range(0, Q, SMALL_Q):
+            part, pv, pr = _panel_of(at, Q, x, vals, rows)
+            scores = self._panel_scores(part, normalize)
+            if middle is not None:
+                scores = middle(at, part, scores)
+            if scores is not None:
+                self._rerank_select(plan, scores, part.shape[0], k, pv, pr)
+        return vals, rows
 
     def _panel_scores(self, part, normalize):
         """at most 32 queries -> the cached score buffer holding their dense product with the gallery (shortlist's first step)"""
@@ -956,8 +974,7 @@ class GalleryIndex:
         bonus-modified buffer: exact by construction.  alpha == 0.0 equals shortlist_pids bit for bit.  Needs pids and a current graph;
         queries, normalize, mask and the capture rule: as search_reranked and shortlist_pids."""
         vals, rows = self._reranked("search_reranked_pids", queries, k, alpha, normalize, mask, distinct=True)
-        pids = self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
-        return vals, rows, pids
+        return vals, rows, self._pids_of(rows)
 
     # ------------------------------------------------------------------ query expansion and database-side augmentation
     def _blend_tables(self):
@@ -995,51 +1012,32 @@ class GalleryIndex:
         return self._check_search(name, queries, 1 if k is None else k, mask, need_pids=need_pids, max_k=MAX_SHORTLIST_K)
 
     def _expanded(self, name, queries, k, m, power, normalize, mask, distinct=False):
-        """expand_queries (k None -> the expanded queries), search_expanded and search_expanded_pids (-> values, rows): one panel
-        loop.  Per panel of 32 queries: the dense product and the deep select with k = m over the allowed rows (shortlist's two
-        steps) = the queries' m best rows and their values; trid_index_blend_rows_f32 with the unit queries as base;
-        trid_l2norm_rows_f32 on the blend; then, for the searches, shortlist's steps again with the expanded queries (or the two
-        distinct-pid steps) and the SAME allow words."""
+        """expand_queries (k None -> the expanded queries), search_expanded and search_expanded_pids (-> values, rows): the panel
+        loop with the expansion as its middle step.  Per panel of 32 queries: the dense product and the deep select with k = m over
+        the allowed rows (shortlist's two steps) = the queries' m best rows and their values; trid_index_blend_rows_f32 with the
+        unit queries as base; trid_l2norm_rows_f32 on the blend; then, for the searches, the product again with the expanded
+        queries and the final select with the SAME allow words."""
         x = self._check_expand(name, queries, k, m, power, mask, need_pids=distinct)
-        Q, G, dev = x.shape[0], self._n, x.device
-        words = self._mask_words(None if mask is None else mask.contiguous()) if (mask is not None or self._dead) else None
-        need = ops.L.load().trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0)
+        plan = self._search_plan(k, mask, distinct, also=(m,))
         qval, qrow, blend, unit = self._expand_buffers()
         tab, lens = self._blend_tables()
-        if k is None:
-            out = torch.empty(Q, self.dim, dtype=torch.float32, device=dev)
-            ws = self._deep_workspace(m)
-        else:
-            vals = torch.empty(Q, k, dtype=torch.float32, device=dev)
-            rows = torch.empty(Q, k, dtype=torch.int64, device=dev)
-            if distinct:
-                table, n_slots, best = self._distinct_setup(k)
-                ws = self._deep_workspace(m, slots=(n_slots, k))
-            else:
-                ws = self._deep_workspace(k, m)
-        for at in range(0, Q, SMALL_Q):  # panels of 32 queries through the one score buffer, into slices of the outputs
-            part = x[at : at + SMALL_Q]
+        out = torch.empty(x.shape[0], self.dim, dtype=torch.float32, device=x.device) if k is None else None
+
+        def expand(at, part, scores):
             Qp = part.shape[0]
-            q16, _ = self._query_panel(part, normalize, need)
             if normalize:
-                base = self._workspace(need)[1]  # (the normalised queries the panel was packed from)
+                base = self._workspace(0)[1]  # (the normalised queries the panel was packed from)
             else:
                 base = part if part.data_ptr() % 16 == 0 else unit[:Qp].copy_(part)  # (the blend reads 16 bytes per lane)
-            scores = self._dense_scores(q16)
             qv, qr = qval[: Qp * m].view(Qp, m), qrow[: Qp * m].view(Qp, m)
-            _deep_topk(_p(scores), 1, scores.shape[1], Qp, G, m, words, qv, qr, ws=ws)
+            self._rerank_own_lists(plan, scores, Qp, m, qv, qr)
             call("trid_index_blend_rows_f32", _p(tab), _p(lens), 1, 0, _p(qr), 8, _p(qv), m, Qp, m, power, _p(base), self.dim, _p(blend), stream())
             new = out[at : at + Qp] if k is None else unit[:Qp]
             call("trid_l2norm_rows_f32", _p(blend), _p(new), None, Qp, self.dim, 1e-12, stream())
-            if k is None:
-                continue
-            q16, _ = self._query_panel(new, False, need)
-            scores = self._dense_scores(q16)
-            if distinct:
-                self._distinct_select(scores, Qp, k, words, table, n_slots, best, ws, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q])
-            else:
-                _deep_topk(_p(scores), 1, scores.shape[1], Qp, G, k, words, vals[at : at + SMALL_Q], rows[at : at + SMALL_Q], ws=ws)
-        return out if k is None else (vals, rows)
+            return None if k is None else self._panel_scores(new, False)
+
+        found = self._deep_panels(x, k, normalize, plan, expand)
+        return out if k is None else found
 
     def expand_queries(self, queries, m=5, power=1, normalize=True, mask=None):
         """-> unit fp32 [Q, 256]: query expansion (AQE for power = 0, its weighted form alpha-QE for power >= 1).  Every query is
@@ -1064,8 +1062,7 @@ class GalleryIndex:
         (the m best allowed ROWS), the second pass selects through the two steps of shortlist_pids; it equals
         shortlist_pids(expand_queries(...), k, normalize=False, mask=mask) bit for bit.  The index must hold pids."""
         vals, rows = self._expanded("search_expanded_pids", queries, k, m, power, normalize, mask, distinct=True)
-        pids = self._pids[: self._n][rows].masked_fill_(rows < 0, -1)
-        return vals, rows, pids
+        return vals, rows, self._pids_of(rows)
 
     def augmented(self, m=None, power=1):
         """-> a NEW GalleryIndex, database-side augmentation (DBA): every live row's embedding becomes the normalised weighted sum of
@@ -1161,9 +1158,8 @@ class GalleryIndex:
             self._dead = n - int(self._live[:n].sum())
         self._n = n
         if nn is not None:
-            self._nn = torch.full((self.capacity, nn.shape[1]), -1, dtype=torch.int32, device=x.device)
+            self._nn, self._nn_val = _graph_pair(self.capacity, nn.shape[1], x.device, values=val is not None)
             self._nn[:n].copy_(nn.to(x.device))
             self._nn_ok, self._nn_rows = True, n
             if val is not None:
-                self._nn_val = torch.full((self.capacity, nn.shape[1]), float("-inf"), dtype=torch.float32, device=x.device)
                 self._nn_val[:n].copy_(val.to(x.device))

@@ -65,7 +65,7 @@ concatenated rows has these lists (ids after the mapping), these values bit for 
     gather and a merge after each phase; not capturable.
   * ``refresh_neighbours()`` -> ``(new_rows, redone_rows)``, in-process only (by rank: RuntimeError naming ``build_neighbours``): per
     part and per group of at most 32 new rows one ``trid_gemm_p16`` product (tile kernel, the group as A, the part's old rows as B)
-    and one ``trid_index_nn_merge_sharded_f32`` (csrc/index_shard_graph.hip: liveness by global id, order by value then global id -
+    and one ``trid_index_nn_merge_sharded_f32`` (csrc/index_nn_update.hip, the kernel of the index's merge with the sharded policy: liveness by global id, order by value then global id -
     the new rows of a middle part are numbered BELOW the stored rows of later parts); removals only: one launch per part with
     m = 0; the new rows' lists from the build's panel step; the flags of all parts read once on the host, flagged rows gathered
     32 at a time, recomputed by the panel step and scattered back.  Lists and values equal a fresh build bit for bit.
@@ -88,10 +88,12 @@ Not built: ``compact`` (it would renumber rows inside a part), the by-rank ``ref
 general, so it can be added), rebalancing rows between ranks, shards on several devices of one process.
 """
 
+from functools import partial
+
 import torch
 
-from . import ops, parallel
-from .index import DIM, MAX_EXPAND, MAX_EXPAND_POWER, MAX_K, MAX_NEIGHBOURS, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex
+from . import index, ops, parallel
+from .index import DIM, MAX_EXPAND, MAX_EXPAND_POWER, MAX_K, MAX_NEIGHBOURS, MAX_ROWS, MAX_SHORTLIST_K, SMALL_Q, GalleryIndex, _blank_dead, _fill_panel, _graph_pair
 from .ops import _p, call, stream
 
 SHARD_BITS = 21
@@ -99,9 +101,18 @@ SHARD_STRIDE = 1 << SHARD_BITS  # global row = shard * SHARD_STRIDE + local row;
 MAX_GRAPH_SHARDS = 1023  # the neighbour graph holds global rows as int32: shard * SHARD_STRIDE + local < 2**31
 
 
-def _need_cuda(name, t):
-    if not t.is_cuda:
-        raise RuntimeError("textreid_amd.index_shards.GalleryShards.%s runs on the HIP kernel library only (CUDA tensors); no CPU fallback" % name)
+_need_cuda = partial(index._need_cuda, owner="index_shards.GalleryShards")
+_ABSENT = ((float("-inf"), torch.float32), (-1, torch.int64), (-1, torch.int64))  # what a slot without a result holds: value, row, pid
+
+
+def _pad_lists(lists, n_out, Q, k, device):
+    """a tuple of [Q, k'] tensors (values, rows[, pids]; k' <= k), or None for no list at all -> ``n_out`` tensors [Q, k] that end in
+    absent slots (-inf, -1[, -1])"""
+    if lists is None:
+        return tuple(torch.full((Q, k), f, dtype=d, device=device) for f, d in _ABSENT[:n_out])
+    if lists[0].shape[1] == k:
+        return tuple(lists[:n_out])
+    return tuple(torch.cat([o, torch.full((Q, k - o.shape[1]), f, dtype=d, device=device)], dim=1) for o, (f, d) in zip(lists[:n_out], _ABSENT))
 
 
 def max_merge_candidates():
@@ -308,18 +319,25 @@ class GalleryShards:
             self._ws["base"] = base
         return buf, base[:S]
 
+    @staticmethod
+    def _stage(bufs, s, got, Q=None):
+        """one part's lists ``got`` - (values, rows[, pids]) of [Q, kk] each, or None: no list - into list s of the staging buffers
+        ``bufs`` (their first Q rows; default: all); the slots behind kk are marked absent (row -1)"""
+        kk = 0 if got is None else got[0].shape[1]
+        for dst, src in zip(bufs, got or ()):
+            if dst is not None:
+                dst[:Q, s, :kk].copy_(src)
+        if kk < bufs[1].shape[2]:
+            bufs[1][:Q, s, kk:].fill_(-1)
+
     def _merge(self, val, row, pid, base, k):
         """[Q, S, kin] candidates -> the first k in the order, padded to k: one launch, or rounds (groups of lists, then the groups'
         results) when S * kin exceeds what one launch takes"""
         Q, S, kin = val.shape
         cap = max_merge_candidates()
         if S * kin <= cap:
-            kk = min(k, S * kin)
-            out = merge_lists(val, row, kk, base, pid)
-            if kk == k:
-                return out
-            fills = (float("-inf"), -1, -1)
-            return tuple(torch.cat([o, torch.full((Q, k - kk), f, dtype=o.dtype, device=o.device)], dim=1) for o, f in zip(out, fills))
+            out = merge_lists(val, row, min(k, S * kin), base, pid)
+            return _pad_lists(out, len(out), Q, k, val.device)
         g = cap // kin
         k2 = min(k, g * kin)
         outs = [self._merge(val[:, at : at + g].contiguous(), row[:, at : at + g].contiguous(), None if pid is None else pid[:, at : at + g].contiguous(),
@@ -329,28 +347,18 @@ class GalleryShards:
 
     def _search(self, name, queries, k, normalize, mask, max_k, distinct):
         x, masks = self._check(name, queries, k, mask, max_k, distinct)
-        Q, dev = x.shape[0], x.device
+        Q, dev, n_out = x.shape[0], x.device, 3 if distinct else 2
         lists = [self._ask(part, name, x, k, normalize, m) for part, m in zip(self._parts, masks)]
         W = parallel.world_size() if self.collective else 1
         if not self.collective and len(lists) == 1 or self.collective and W == 1:
             # one shard: the part's answer is the answer (global row = local row + this shard's base), padded to k
             got, off = lists[0], self.shard * SHARD_STRIDE
-            fills = (float("-inf"), -1, -1)[: 3 if distinct else 2]
-            dts = (torch.float32, torch.int64, torch.int64)
-            if got is None:
-                return tuple(torch.full((Q, k), f, dtype=d, device=dev) for f, d in zip(fills, dts))
-            if off:
+            if got is not None and off:
                 got = (got[0], torch.where(got[1] < 0, got[1], got[1] + off)) + tuple(got[2:])
-            if got[0].shape[1] == k:
-                return tuple(got)
-            return tuple(torch.cat([o, torch.full((Q, k - o.shape[1]), f, dtype=o.dtype, device=dev)], dim=1) for o, f in zip(got, fills))
+            return _pad_lists(got, n_out, Q, k, dev)
         if self.collective:
             # this rank's list padded to k with absent slots, gathered rank-major, [W * Q, k] -> [Q, W, k]
-            mine = [torch.full((Q, k), f, dtype=d, device=dev) for f, d in zip((float("-inf"), -1, -1), (torch.float32, torch.int64, torch.int64))]
-            if lists[0] is not None:
-                for dst, src in zip(mine, lists[0]):
-                    dst[:, : src.shape[1]].copy_(src)
-            cand = [parallel.all_gather_rows(t).view(W, Q, k).permute(1, 0, 2).contiguous() for t in mine[: 3 if distinct else 2]]
+            cand = [parallel.all_gather_rows(t).view(W, Q, k).permute(1, 0, 2).contiguous() for t in _pad_lists(lists[0], n_out, Q, k, dev)]
             base = torch.arange(W, dtype=torch.int64, device=dev) * SHARD_STRIDE
             return self._merge(cand[0], cand[1], cand[2] if distinct else None, base, k)
         S = len(lists)
@@ -358,14 +366,7 @@ class GalleryShards:
         kin = max(widest, -(-k // S))  # (S * kin >= k: the merge's own k rule)
         (val, row, pid), base = self._staging(Q, S, kin, distinct, dev)
         for s, got in enumerate(lists):
-            kk = 0 if got is None else got[0].shape[1]
-            if kk:
-                val[:, s, :kk].copy_(got[0])
-                row[:, s, :kk].copy_(got[1])
-                if distinct:
-                    pid[:, s, :kk].copy_(got[2])
-            if kk < kin:
-                row[:, s, kk:].fill_(-1)
+            self._stage((val, row, pid), s, got)
         return self._merge(val, row, pid, base, k)
 
     def search(self, queries, k=10, normalize=True, mask=None):
@@ -390,7 +391,7 @@ class GalleryShards:
         """-> (part addresses int64 [S], part lengths int64 [S]) on the device: the parts' fp32 row storages as the address table of
         trid_index_blend_rows_f32 (shift = SHARD_BITS: a global row decodes to its part and local row).  Cached; rebuilt - one small
         upload, outside any capture - when a part's storage or length changed.  A part without storage has length 0."""
-        key = tuple((0, 0) if p._rows is None else (p._rows.data_ptr(), len(p)) for p in self._parts)
+        key = tuple((0, 0) if p.rows is None else (p.rows.data_ptr(), len(p)) for p in self._parts)
         if self._ws.get("blend_key") != key:
             self._ws["blend_tab"] = torch.tensor([[a for a, _ in key], [n for _, n in key]], dtype=torch.int64, device=dev)
             self._ws["blend_key"] = key
@@ -442,7 +443,7 @@ class GalleryShards:
     # ------------------------------------------------------------------ neighbour graph over the shards
     def _sig(self):
         """(len, removed rows) of every part: what a graph is current FOR (add and remove change it, wherever they were called)"""
-        return [(len(p), p._dead) for p in self._parts]
+        return [(len(p), len(p) - p.live_count) for p in self._parts]
 
     @property
     def neighbours(self):
@@ -480,32 +481,25 @@ class GalleryShards:
         dev = next((p.device for p in self._parts if p.device is not None), self._g_nn[0].device)
         for s, part in enumerate(self._parts):
             want = max(part.capacity, MAX_NEIGHBOURS)
-            if s < len(self._g_nn) and self._g_nn[s].shape[0] >= want:
-                continue
-            nn = torch.full((want, n), -1, dtype=torch.int32, device=dev)
-            val = None if self._g_val is None else torch.full((want, n), float("-inf"), dtype=torch.float32, device=dev)
-            if s < len(self._g_nn):
-                held = self._g_nn[s].shape[0]
-                nn[:held].copy_(self._g_nn[s])
-                self._g_nn[s] = nn
-                if val is not None:
-                    val[:held].copy_(self._g_val[s])
-                    self._g_val[s] = val
-            else:
+            if s == len(self._g_nn):  # (a part opened since)
+                nn, val = _graph_pair(want, n, dev, values=self._g_val is not None)
                 self._g_nn.append(nn)
                 if val is not None:
                     self._g_val.append(val)
+            elif self._g_nn[s].shape[0] < want:
+                old = (self._g_nn[s], None if self._g_val is None else self._g_val[s])
+                nn, val = _graph_pair(want, n, dev, old=old, rows=old[0].shape[0])
+                self._g_nn[s] = nn
+                if val is not None:
+                    self._g_val[s] = val
 
     def _fill_panel(self, src, Q, dev):
-        """Q < 32 P16 rows into the shards' own cached zero-padded [32, 256] panel (bit copies: the rows carry the fixed unit scale)"""
+        """Q < 32 P16 rows into the shards' own cached zero-padded [32, 256] panel (a part's cached panel carries that part's state)"""
         q16 = self._ws.get("panel")
         if q16 is None or q16.device != dev:
             q16 = torch.zeros(SMALL_Q, DIM, dtype=torch.float32, device=dev)
             self._ws["panel"], self._ws["panel_rows"] = q16, 0
-        q16.view(torch.int32)[:Q].copy_(src.view(torch.int32))
-        if Q < self._ws["panel_rows"]:
-            q16[Q : self._ws["panel_rows"]].zero_()
-        self._ws["panel_rows"] = Q
+        self._ws["panel_rows"] = _fill_panel(q16, src, Q, self._ws["panel_rows"])
         return q16
 
     def _panel_tmp(self, n, dev):
@@ -519,16 +513,9 @@ class GalleryShards:
     @staticmethod
     def _one_pass(part, panel, Q, kk, vals, rows):
         """one one-pass search of ``part`` with the Q rows of ``panel`` as the queries, k = kk <= part.live_count -> vals / rows [Q, kk]
-        (local rows): the masked form once the part has removed rows, as GalleryIndex._neighbour_search"""
-        G = len(part)
-        L = ops.L.load()
-        need = max(L.trid_index_search_ws_bytes(G, SMALL_Q, MAX_K, 0), L.trid_index_search_ws_bytes(G, SMALL_Q, kk, 0))
-        lists = part._workspace(need)[3]
-        if part._dead:
-            call("trid_index_search_masked_p16", _p(panel), _p(part._p16), _p(part._unit), _p(part._mask_words(None)), Q, G, kk, 0, _p(vals), _p(rows),
-                 _p(lists), 0, stream())
-        else:
-            call("trid_index_search_p16", _p(panel), _p(part._p16), _p(part._unit), Q, G, kk, 0, _p(vals), _p(rows), _p(lists), 0, stream())
+        (local rows): the masked form once the part has removed rows"""
+        _, lists, words = part._neighbour_workspace(kk)
+        part._one_pass(panel, Q, kk, vals, rows, lists, words)
 
     def _graph_panel(self, panel, Q, n):
         """the panel step of the build: the Q <= 32 P16 rows of ``panel`` as the queries of one one-pass search per part at k = min(n,
@@ -540,13 +527,11 @@ class GalleryShards:
         tv, tr = self._panel_tmp(n, dev)
         for t, other in enumerate(parts):
             kk = min(n, other.live_count) if len(other) else 0
+            got = None
             if kk:
-                ov, orow = tv[: Q * kk].view(Q, kk), tr[: Q * kk].view(Q, kk)
-                self._one_pass(other, panel, Q, kk, ov, orow)
-                val[:Q, t, :kk].copy_(ov)
-                row[:Q, t, :kk].copy_(orow)
-            if kk < n:
-                row[:Q, t, kk:].fill_(-1)
+                got = tv[: Q * kk].view(Q, kk), tr[: Q * kk].view(Q, kk)
+                self._one_pass(other, panel, Q, kk, *got)
+            self._stage((val, row), t, got, Q)
         return merge_lists(val[:Q], row[:Q], n, base)
 
     def _graph_rows(self, s, first, last, n):
@@ -556,14 +541,12 @@ class GalleryShards:
         nn, val = self._g_nn[s], self._g_val[s]
         for at in range(first, last, SMALL_Q):
             Q = min(SMALL_Q, last - at)
-            panel = part._p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part._p16[at : at + Q], Q, part.device)
+            panel = part.rows_p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part.rows_p16[at : at + Q], Q, part.device)
             v, r = self._graph_panel(panel, Q, n)
             nn[at : at + Q].copy_(r)  # (narrowed: global ids of at most 1023 shards fit int32)
             val[at : at + Q].copy_(v)
-        if part._dead:
-            dead = ~part._live[first:last, None]
-            nn[first:last].masked_fill_(dead, -1)
-            val[first:last].masked_fill_(dead, float("-inf"))
+        if part.live_count < len(part):
+            _blank_dead(nn[first:last], val[first:last], part.live[first:last])
 
     def _check_build(self, name, n):
         if not isinstance(n, int) or n < 1 or n > MAX_NEIGHBOURS:
@@ -588,8 +571,7 @@ class GalleryShards:
         if n > self.live_count:
             raise ValueError("GalleryShards.build_neighbours: n must be <= live_count = %d; got %d" % (self.live_count, n))
         dev = next(p.device for p in self._parts if len(p))
-        self._g_nn = [torch.full((max(p.capacity, MAX_NEIGHBOURS), n), -1, dtype=torch.int32, device=dev) for p in self._parts]
-        self._g_val = [torch.full((max(p.capacity, MAX_NEIGHBOURS), n), float("-inf"), dtype=torch.float32, device=dev) for p in self._parts]
+        self._g_nn, self._g_val = map(list, zip(*[_graph_pair(max(p.capacity, MAX_NEIGHBOURS), n, dev) for p in self._parts]))
         self._g_sig = None
         for s, part in enumerate(self._parts):
             if len(part):
@@ -609,8 +591,7 @@ class GalleryShards:
             raise ValueError("GalleryShards.build_neighbours: n must be <= live_count = %d; got %d" % (int(counts[:, 1].sum()), n))
         G = len(part)
         kk = min(n, part.live_count) if G else 0
-        nn = torch.full((max(part.capacity, MAX_NEIGHBOURS), n), -1, dtype=torch.int32, device=dev)
-        val = torch.full((max(part.capacity, MAX_NEIGHBOURS), n), float("-inf"), dtype=torch.float32, device=dev)
+        nn, val = _graph_pair(max(part.capacity, MAX_NEIGHBOURS), n, dev)
         zero = torch.zeros(SMALL_Q, DIM, dtype=torch.float32, device=dev)
         cv = torch.empty(W * SMALL_Q, n, dtype=torch.float32, device=dev)
         cr = torch.empty(W * SMALL_Q, n, dtype=torch.int64, device=dev)
@@ -618,7 +599,7 @@ class GalleryShards:
         base = torch.arange(W, dtype=torch.int64, device=dev) * SHARD_STRIDE
         for at in range(0, int(counts[:, 0].max()), SMALL_Q):
             Q = max(0, min(SMALL_Q, G - at))
-            mine = zero if Q == 0 else part._p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part._p16[at : at + Q], Q, dev)
+            mine = zero if Q == 0 else part.rows_p16[at : at + SMALL_Q] if Q == SMALL_Q else self._fill_panel(part.rows_p16[at : at + Q], Q, dev)
             panels = parallel.all_gather_rows(mine.view(torch.int32)).view(torch.float32)  # [W * 32, 256]: bit copies of P16 rows
             cr.fill_(-1)
             for w in range(W):
@@ -635,10 +616,8 @@ class GalleryShards:
                 v, rows = merge_lists(gv[:Q], gr[:Q], n, base)
                 nn[at : at + Q].copy_(rows)
                 val[at : at + Q].copy_(v)
-        if G and part._dead:
-            dead = ~part._live[:G, None]
-            nn[:G].masked_fill_(dead, -1)
-            val[:G].masked_fill_(dead, float("-inf"))
+        if G and part.live_count < G:
+            _blank_dead(nn[:G], val[:G], part.live)
         self._g_nn, self._g_val, self._g_sig = [nn], [val], self._sig()
 
     def refresh_neighbours(self):
@@ -670,7 +649,7 @@ class GalleryShards:
         lens = [len(p) for p in parts]
         old = [min(c, g) for (c, _), g in zip(self._g_sig or [], lens)] + [0] * (S - len(self._g_sig or []))
         dev = next(p.device for p in parts if len(p))
-        live_all = torch.cat([p._live[:g].view(torch.uint8) for p, g in zip(parts, lens) if g])  # (bool storage: one byte per row, 0 / 1)
+        live_all = torch.cat([p.live.view(torch.uint8) for p, g in zip(parts, lens) if g])  # (bool storage: one byte per row, 0 / 1)
         offs = [sum(lens[:s]) for s in range(S)]
         live_off = torch.tensor(offs, dtype=torch.int64, device=dev)
         live_len = torch.tensor(lens, dtype=torch.int32, device=dev)
@@ -689,10 +668,7 @@ class GalleryShards:
             if not groups:
                 merge(None, 0, 0)
             for t, at, m in groups:
-                # the direction and the kernel of GalleryIndex._candidate_scores; the A panel comes from part t
-                cand = part._score_buffer(part._ws.get("cols", SMALL_Q))  # (capacity * cols >= 32 * n0 floats)
-                ops.gemm_p16(ops.P16(parts[t]._p16[at : at + m], parts[t]._unit), ops.P16(part._p16[:n0], part._unit), cand, m, n0, DIM, n0, tile_only=True)
-                merge(cand, m, t * SHARD_STRIDE + at)
+                merge(part._candidate_scores(at, m, n0, src=parts[t]), m, t * SHARD_STRIDE + at)  # (the A panel comes from part t)
         for t in range(S):
             if lens[t] > old[t]:
                 self._graph_rows(t, old[t], lens[t], n)
@@ -702,10 +678,10 @@ class GalleryShards:
             for at in range(0, own.numel(), SMALL_Q):
                 rows = own[at : at + SMALL_Q]
                 Q = rows.numel()
-                v, r = self._graph_panel(self._fill_panel(part._p16.view(torch.int32)[rows], Q, dev), Q, n)
+                v, r = self._graph_panel(self._fill_panel(part.rows_p16.view(torch.int32)[rows], Q, dev), Q, n)
                 self._g_nn[s][rows] = r.int()
                 self._g_val[s][rows] = v
-        new_rows = sum(int(parts[t]._live[old[t] : lens[t]].sum()) for t in range(S) if lens[t] > old[t])
+        new_rows = sum(int(parts[t].live[old[t] :].sum()) for t in range(S) if lens[t] > old[t])
         self._g_sig = self._sig()
         return new_rows, int(again.numel())
 
@@ -734,9 +710,9 @@ class GalleryShards:
         parts, S = self._parts, len(self._parts)
         Q, dev, n = x.shape[0], x.device, self._g_nn[0].shape[1]
         # a part is asked for min(k, what it holds), as in the other searches; one with no live row contributes absent lists.  A part
-        # with fewer rows than n is walked as n rows, the extra ones masked off (GalleryIndex._rerank_plan)
+        # with fewer rows than n is walked as n rows, the extra ones masked off (GalleryIndex._search_plan)
         ks = [0 if len(p) == 0 or p.live_count == 0 else min(k, len(p) if m is not None else p.live_count) for p, m in zip(parts, masks)]
-        plans = [p._rerank_plan(kk, n, m, distinct, extent=n) if kk else None for p, m, kk in zip(parts, masks, ks)]
+        plans = [p._search_plan(kk, m, distinct, also=(n,), extent=n) if kk else None for p, m, kk in zip(parts, masks, ks)]
         kin = k if self.collective else max(max(ks), -(-k // S))
         outs = [torch.empty(Q, k, dtype=d, device=dev) for d in (torch.float32, torch.int64, torch.int64)[: 3 if distinct else 2]]
         own = [(torch.empty(SMALL_Q, n, dtype=torch.float32, device=dev), torch.empty(SMALL_Q, n, dtype=torch.int64, device=dev)) if kk else None for kk in ks]
@@ -747,28 +723,23 @@ class GalleryShards:
             Qp = xp.shape[0]
             (sv, sr, _), base = self._staging(Qp, S, n, False, dev)
             for s, part in enumerate(parts):
+                got = None
                 if ks[s]:
                     scores[s] = part._panel_scores(xp, normalize)
-                    qv, qn = own[s][0][:Qp], own[s][1][:Qp]
-                    part._rerank_own_lists(plans[s], scores[s], Qp, n, qv, qn)
-                    sv[:, s].copy_(qv)
-                    sr[:, s].copy_(qn)
-                else:
-                    sr[:, s].fill_(-1)
+                    got = own[s][0][:Qp], own[s][1][:Qp]
+                    part._rerank_own_lists(plans[s], scores[s], Qp, n, *got)
+                self._stage((sv, sr), s, got)
             qnn = self._combine(sv, sr, None, base, n)[1]  # the queries' own lists, GLOBAL rows, int64 [Qp, n]
             (fv, fr, fp), base = self._staging(Qp, S, kin, distinct, dev)
             for s, part in enumerate(parts):
-                kk = ks[s]
+                kk, got = ks[s], None
                 if kk:
                     part._rerank_bonus(plans[s], scores[s], Qp, qnn, self._g_nn[s], n, alpha)
-                    ov, orow = tmp[s][0][: Qp * kk].view(Qp, kk), tmp[s][1][: Qp * kk].view(Qp, kk)
-                    part._rerank_select(plans[s], scores[s], Qp, kk, ov, orow)
-                    fv[:, s, :kk].copy_(ov)
-                    fr[:, s, :kk].copy_(orow)
+                    got = tmp[s][0][: Qp * kk].view(Qp, kk), tmp[s][1][: Qp * kk].view(Qp, kk)
+                    part._rerank_select(plans[s], scores[s], Qp, kk, *got)
                     if distinct:
-                        fp[:, s, :kk].copy_(part._pids[: len(part)][orow].masked_fill_(orow < 0, -1))
-                if kk < kin:
-                    fr[:, s, kk:].fill_(-1)
+                        got += (part._pids_of(got[1]),)
+                self._stage((fv, fr, fp), s, got)
             for dst, src in zip(outs, self._combine(fv, fr, fp, base, k)):
                 dst[at : at + Qp].copy_(src)
         return tuple(outs)
@@ -812,12 +783,10 @@ class GalleryShards:
         n = nn[0].shape[1]
         g_nn, g_val = [], None if val is None else []
         for s, part in enumerate(parts):
-            want = max(part.capacity, MAX_NEIGHBOURS)
-            a = torch.full((want, n), -1, dtype=torch.int32, device=dev)
+            a, b = _graph_pair(max(part.capacity, MAX_NEIGHBOURS), n, dev, values=val is not None)
             a[: len(part)].copy_(nn[s].to(dev))
             g_nn.append(a)
             if val is not None:
-                b = torch.full((want, n), float("-inf"), dtype=torch.float32, device=dev)
                 b[: len(part)].copy_(val[s].to(dev))
                 g_val.append(b)
         return g_nn, g_val
