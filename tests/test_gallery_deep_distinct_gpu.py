@@ -14,52 +14,12 @@ import gallery_deep_distinct_ref as DR  # noqa: E402
 import gallery_rerank_ref as RR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
+from gallery_support import dense_product, fresh_index, gpu, Inputs, same_bits as same, unit_rows, words_tensor  # noqa: E402,F401
 
 SEED = 14
 ABSENT = DR.ABSENT
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def dense_product(idx, q_unit):
-    """-> fp32 [Q, len] on the host: trid_gemm_p16 with the index's P16 gallery as A and the zero-padded query panel (32 queries at a
-    time, packed with the index's unit scalar as search packs it) as B - 64 panel rows if the tile kernel declines 32 columns"""
-    from textreid_amd import ops
-
-    G, dev = len(idx), q_unit.device
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    out = []
-    for at in range(0, q_unit.shape[0], 32):
-        part = q_unit[at : at + 32].contiguous()
-        sim = None
-        for cols in (32, 64):
-            panel = torch.zeros(cols, 256, device=dev)
-            panel[: part.shape[0]] = ops.p16_pack(part, amax_=idx.unit_amax).data
-            C = torch.empty(G, cols, device=dev)
-            try:
-                ops.gemm_p16(A, ops.P16(panel, idx.unit_amax), C, G, cols, 256, cols)
-            except RuntimeError:
-                continue
-            sim = C[:, : part.shape[0]].t().contiguous().cpu()
-            break
-        assert sim is not None
-        out.append(sim)
-    return torch.cat(out, dim=0)
-
-
-def same(got, want, what=""):
-    assert TR.same((got[0].cpu().numpy(), got[1].cpu().numpy()), (np.asarray(want[0]), np.asarray(want[1]))), what
+IN = Inputs("gdd:", SEED)
+coin, gallery, queries = IN.coin_one_in, IN.gallery, IN.queries
 
 
 def same3(got, want, pids, what=""):
@@ -68,23 +28,6 @@ def same3(got, want, pids, what=""):
     rows = np.asarray(want[1])
     want_pids = np.where(rows >= 0, np.asarray(pids)[np.maximum(rows, 0)], -1)
     assert got[2].dtype == torch.int64 and np.array_equal(got[2].cpu().numpy(), want_pids), what
-
-
-def coin(name, n, one_in=2):
-    return OF.randint("gdd:" + name, 0, one_in, (n,), SEED) != 0 if one_in == 2 else OF.randint("gdd:" + name, 0, one_in, (n,), SEED) == 0
-
-
-def words_tensor(allowed, gpu, garbage=True, seed=0):
-    """the packed allow words of a bool [G] array; the tail bits of the last word are garbage (they must be ignored)"""
-    G = allowed.size
-    nw = (G + 31) // 32
-    bits = np.zeros(nw * 32, dtype=np.uint64)
-    bits[:G] = allowed
-    if garbage and nw * 32 > G:
-        bits[G:] = np.random.RandomState(seed).randint(0, 2, size=nw * 32 - G)
-        bits[G] = 1
-    w = (bits.reshape(nw, 32) << np.arange(32, dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint32)
-    return torch.from_numpy(w.view(np.int32).copy()).to(gpu)
 
 
 def level_matrix(Q, G, levels, seed, specials=True):
@@ -132,7 +75,7 @@ def run_group_best(gpu, sim, order, starts, n_groups, n_slots, layout, allowed=N
     dv, dr = torch.from_numpy(ov).to(gpu), torch.from_numpy(orow).to(gpu)
     dev = torch.from_numpy(buf).to(gpu)
     d_order, d_starts = torch.from_numpy(np.asarray(order, dtype=np.int32)).to(gpu), torch.from_numpy(np.asarray(starts, dtype=np.int32)).to(gpu)
-    words = None if allowed is None else words_tensor(allowed, gpu, seed=G)
+    words = None if allowed is None else words_tensor(allowed, gpu, garbage=True, seed=G)
     ops.call("trid_index_group_best_f32", _p(dev), ld_q, ld_g, Q, G, _p(d_order), _p(d_starts), n_groups, n_slots, _p(words), _p(dv), _p(dr),
              o_q, o_g, ops.stream())
     gv, gr = dv.cpu().numpy(), dr.cpu().numpy()
@@ -334,30 +277,9 @@ def test_pairs_select_with_numbered_columns_is_the_row_select(gpu, G, k, chunk):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the index
-_built = {}
-
-
-def gallery(G):
-    if G not in _built:
-        _built[G] = OF.randn("gdd:g%d" % G, (G, 256), SEED)
-    return _built[G]
-
-
 def some_pids(G, per=4, tag="p"):
     """about `per` rows per pid, scattered; pid values far apart (the group numbering must not depend on them)"""
     return OF.randint("gdd:%s%d" % (tag, G), 0, max(G // per, 1), (G,), SEED).long() * 1000003 - 77
-
-
-def fresh_index(gpu, rows, pids):
-    from textreid_amd import GalleryIndex
-
-    idx = GalleryIndex()
-    idx.add(rows.to(gpu), pids=pids)
-    return idx
-
-
-def queries(gpu, Q, tag="q"):
-    return unit_rows(OF.randn("gdd:%s%d" % (tag, Q), (Q, 256), SEED).to(gpu))
 
 
 class Ref:

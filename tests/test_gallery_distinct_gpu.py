@@ -1,6 +1,7 @@
 """GalleryIndex.search_pids on the GPU: the exact top-k over distinct pids in the one-pass kernel.  The comparator is exact, as in
-test_gallery_mask_gpu.py: the dense trid_gemm_p16 product of the index's own P16 operands, then gallery_distinct_ref.distinct_topk
-(stable descending sort, the first allowed row of every group, -inf rows reported as -1).  Values and rows are compared bit for bit."""
+test_gallery_mask_gpu.py: the dense trid_gemm_p16 product of the index's own P16 operands (gallery_support.dense_product), then
+gallery_distinct_ref.distinct_topk (stable descending sort, the first allowed row of every group, -inf rows reported as -1).  Values
+and rows are compared bit for bit."""
 
 import pytest
 import torch
@@ -10,92 +11,14 @@ pytestmark = pytest.mark.gpu
 import gallery_distinct_ref as DR  # noqa: E402
 import gallery_mask_ref as MR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
+from gallery_support import c_search, dense_product, fresh_index, gpu, Inputs, same_values as same, unit_rows  # noqa: E402,F401
 
 SEED = 8
 SHAPES = [(1, 1, 1), (2, 33, 10), (5, 63, 5), (32, 64, 16), (7, 65, 10), (5, 4099, 16), (17, 20037, 10)]
 ADV_G = 20037
 NEG = float("-inf")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
-
-
-def raw(Q, G, seed=SEED):
-    return OF.randn("gmk:q%d" % Q, (Q, 256), seed), OF.randn("gmk:g%d" % G, (G, 256), seed)
-
-
-def coin(name, n, keep_of=2, seed=SEED):
-    """bool [n], true with probability 1 / keep_of, drawn from the name"""
-    return OF.randint("gds:" + name, 0, keep_of, (n,), seed) == 0
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def query_panel(idx, q_unit, rows=32):
-    """the zero-padded P16 query panel, packed with the index's unit scalar as the searches pack it"""
-    from textreid_amd import ops
-
-    panel = torch.zeros(rows, 256, device=q_unit.device)
-    panel[: q_unit.shape[0]] = ops.p16_pack(q_unit.contiguous(), amax_=idx.unit_amax).data
-    return panel
-
-
-def dense_sim(idx, q_unit):
-    """trid_gemm_p16 with the index's P16 gallery (removed rows included) as A and zero-padded panels of 32 queries as B
-    -> sim [Q, G] on the CPU: the similarities the one-pass kernel must reproduce bit for bit"""
-    from textreid_amd import ops
-
-    G, Q = len(idx), q_unit.shape[0]
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    out = []
-    for at in range(0, Q, 32):
-        part = q_unit[at : at + 32]
-        sim = None
-        for cols in (32, 64):  # (a 64-row panel if the tile kernel declines 32 columns)
-            B = ops.P16(query_panel(idx, part, cols), idx.unit_amax)
-            C = torch.empty(G, cols, device=q_unit.device)
-            try:
-                ops.gemm_p16(A, B, C, G, cols, 256, cols)
-            except RuntimeError:
-                continue
-            sim = C[:, : part.shape[0]].t().contiguous().cpu()
-            break
-        assert sim is not None
-        out.append(sim)
-    return torch.cat(out, dim=0)
-
-
-def c_search(idx, q_unit, k, workgroups, gid, allow=None):
-    """trid_index_search_distinct_p16 itself with a forced number of workers; gid: any int32 labels; allow None: NULL mask_words"""
-    from textreid_amd import lib as L
-    from textreid_amd.ops import _p, stream
-
-    Q, G = q_unit.shape[0], len(idx)
-    dev = q_unit.device
-    q16 = query_panel(idx, q_unit)
-    nws = L.load().trid_index_search_ws_bytes(G, Q, k, workgroups)
-    assert nws > 0
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    vals = torch.full((Q, k), float("nan"), device=dev)
-    rows = torch.full((Q, k), -7, dtype=torch.int64, device=dev)
-    ids = gid.to(torch.int32).to(dev)
-    assert ids.numel() == G
-    words = None
-    if allow is not None:
-        w = MR.pack_words(allow)  # (made on the CPU, not by the pack kernel)
-        words = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32).to(dev)
-        assert words.numel() == (G + 31) // 32  # exactly the words the contract names
-    L.call("trid_index_search_distinct_p16", _p(q16), _p(idx.rows_p16), _p(idx.unit_amax), _p(ids), _p(words), Q, G, k, 0, _p(vals), _p(rows),
-           _p(ws), workgroups, stream())
-    return vals.cpu(), rows.cpu()
+IN = Inputs("gds:", SEED, raw_tag="gmk:")  # (the raw queries and galleries carry the names of test_gallery_mask_gpu.py; no cache entry is shared)
+coin = IN.coin_keep
 
 
 def relabel(pids):
@@ -105,37 +28,11 @@ def relabel(pids):
     return group_ids(pids) * -7 + 3
 
 
-def fresh_index(gpu, ie, pids=None, **kw):
-    from textreid_amd import GalleryIndex
-
-    idx = GalleryIndex()
-    assert idx.add(ie.to(gpu), pids=pids, **kw) == 0 and len(idx) == ie.shape[0]
-    return idx
-
-
-_built = {}
-
-
 def built(gpu, Q, G):
     """the seed-8 queries and gallery of the shape (on the device too), an index over the gallery WITHOUT pids that no test modifies,
     the dense similarities: computed once, shared, left unchanged"""
-    key = (Q, G)
-    if key not in _built:
-        te, ie = raw(Q, G)
-        ieg = ie.to(gpu)
-        idx = fresh_index(gpu, ieg)
-        qu = unit_rows(te.to(gpu))
-        _built[key] = (idx, te.to(gpu), ieg, qu, dense_sim(idx, qu))
-    return _built[key]
-
-
-def same(got, ref, what, pids=None):
-    gv, gr = got[0].cpu(), got[1].cpu()
-    assert torch.equal(gr, ref[1]), (what, "rows", gr, ref[1])
-    assert torch.equal(gv, ref[0]), (what, "values", gv, ref[0])
-    if pids is not None:  # the third output of search_pids: the pids of the rows, -1 in the short slots
-        want = torch.where(ref[1] >= 0, pids[ref[1].clamp(min=0)], torch.full_like(ref[1], -1))
-        assert got[2].dtype == torch.int64 and torch.equal(got[2].cpu(), want), (what, "pids", got[2], want)
+    idx, te, ie, qu, sim = IN.built(gpu, Q, G)
+    return idx, te.to(gpu), ie.to(gpu), qu, sim
 
 
 def ones(G):
@@ -173,8 +70,8 @@ def test_search_pids_equals_distinct_topk_of_the_dense_product(gpu, Q, G, k):
             assert torch.equal(got[0], plain[0]) and torch.equal(got[1], plain[1])
         gid = relabel(pid)
         for wg in (0, 1, 3):
-            same(c_search(idx, qu, k, wg, gid), ref, "%s workgroups=%d" % (name, wg))
-        same(c_search(idx, qu, k, 3, gid, ones(G)), ref, "%s workgroups=3, all-ones words" % name)
+            same(c_search(idx, qu, k, wg, gid=gid), ref, "%s workgroups=%d" % (name, wg))
+        same(c_search(idx, qu, k, 3, ones(G), gid=gid), ref, "%s workgroups=3, all-ones words" % name)
         same(idx.search(te, k=k), (plain[0].cpu(), plain[1].cpu()), "search on the index that answered search_pids")
     same(plain_idx.search(te, k=k), (plain[0].cpu(), plain[1].cpu()), "search again")
 
@@ -195,7 +92,7 @@ def test_a_crowd_of_one_person_leaves_room_for_fifteen_others(gpu):
     idx = fresh_index(gpu, ieg, pids=pid)
     same(idx.search_pids(te, k=k), ref, "crowd", pid)
     for wg in (0, 1, 3):
-        same(c_search(idx, qu, k, wg, relabel(pid)), ref, "crowd workgroups=%d" % wg)
+        same(c_search(idx, qu, k, wg, gid=relabel(pid)), ref, "crowd workgroups=%d" % wg)
 
 
 # ------------------------------------------------------------------------------------------------------------- 3. ties
@@ -218,7 +115,7 @@ def test_ties_go_to_the_lower_row_inside_a_pid_and_between_pids(gpu):
     for name, pid in (("together", together), ("apart", apart)):
         idx = fresh_index(gpu, g.to(gpu), pids=pid, normalize=False)
         if sim is None:
-            sim = dense_sim(idx, qg)
+            sim = dense_product(idx, qg)
             assert torch.equal(sim[:, :10000], sim[:, 10000:20000])
         ref = DR.distinct_topk(sim, pid, ones(ADV_G), k)
         if name == "together":  # the original represents the pair: no copy is returned, and the values are those of the row search
@@ -229,7 +126,7 @@ def test_ties_go_to_the_lower_row_inside_a_pid_and_between_pids(gpu):
             assert int(pairs.sum()) >= 5
         same(idx.search_pids(qg, k=k, normalize=False), ref, "ties %s" % name, pid)
         for wg in (0, 1, 3):
-            same(c_search(idx, qg, k, wg, relabel(pid)), ref, "ties %s workgroups=%d" % (name, wg))
+            same(c_search(idx, qg, k, wg, gid=relabel(pid)), ref, "ties %s workgroups=%d" % (name, wg))
 
 
 # ------------------------------------------------------------------------------------------------------ 4. composition
@@ -265,7 +162,7 @@ def test_search_pids_with_a_mask(gpu, Q, G, k):
         same(idx.search_pids(te, k=k, mask=allow.to(gpu)), ref, "search_pids(mask) %s" % name, pid)
         same(idx.search_pids(qu, k=k, normalize=False, mask=allow.to(torch.uint8).to(gpu)), ref, "uint8 mask, unit queries, %s" % name, pid)
         for wg in (1, 3):
-            same(c_search(idx, qu, k, wg, relabel(pid), allow), ref, "%s workgroups=%d" % (name, wg))
+            same(c_search(idx, qu, k, wg, allow, gid=relabel(pid)), ref, "%s workgroups=%d" % (name, wg))
     assert idx.live_count == G
     after = idx.search(te, k=k)
     assert torch.equal(before[0], after[0]) and torch.equal(before[1], after[1])
@@ -295,7 +192,7 @@ def test_removing_a_representative_and_removing_a_pid(gpu):
     same(got, DR.distinct_topk(sim, pid, allow & m, k), "tombstones & mask", pid)
     assert got[1][0, :2].tolist() == [c, d]
     for wg in (1, 3):
-        same(c_search(idx, qu, k, wg, relabel(pid), allow & m), DR.distinct_topk(sim, pid, allow & m, k), "tombstones & mask workgroups=%d" % wg)
+        same(c_search(idx, qu, k, wg, allow & m, gid=relabel(pid)), DR.distinct_topk(sim, pid, allow & m, k), "tombstones & mask workgroups=%d" % wg)
     # every row of the person goes: the person is absent
     assert idx.remove(pids=[7]) == 2
     allow[[b, c]] = False
@@ -385,7 +282,7 @@ def test_search_pids_records_and_replays(gpu):
     vb, rb, pb = idx.search_pids(qb, k=k, mask=mb)
     assert torch.equal(got[0], vb) and torch.equal(got[1], rb) and torch.equal(got[2], pb) and not torch.equal(rb, ra)
     allow = (mb & idx.live).cpu()
-    same(got, DR.distinct_topk(dense_sim(idx, unit_rows(qb)), pid, allow, k), "replay against the reference", pid)
+    same(got, DR.distinct_topk(dense_product(idx, unit_rows(qb)), pid, allow, k), "replay against the reference", pid)
     # the mask alone changes the answer too: queries a with mask b
     buf.copy_(qa)
     g.replay()

@@ -13,17 +13,13 @@ pytestmark = pytest.mark.gpu
 import gallery_expand_ref as XR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
-from test_gallery_rerank_gpu import CLUSTER_SEED, coin, dense_product, fresh_index, gallery, queries, same, shared_index, unit_rows  # noqa: E402
+from gallery_support import dense_product, fresh_index, gpu, Inputs, same_bits as same, unit_rows  # noqa: E402,F401
 
 SEED = 17
+CLUSTER_SEED = 15  # (the clustered gallery of test_gallery_rerank_gpu.py: the same names, the same seed)
+IN = Inputs("grr:", 13, graph_n=5)  # (the galleries, queries and coins of test_gallery_rerank_gpu.py, by name: the caches are shared with it)
+coin, gallery, queries, shared_index = IN.coin_one_in, IN.gallery, IN.queries, IN.shared_index
 INT_MAX = 0x7FFFFFFF
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
 
 
 def bits_equal(a, b):
@@ -267,7 +263,7 @@ def clustered(gpu):
         rows = centres.repeat_interleave(8, dim=0) + noise * OF.randn("grr:cnoise", (2000, 256), CLUSTER_SEED)
         rows = rows[torch.from_numpy(np.argsort(OF.randn("grr:cperm", (2000,), CLUSTER_SEED).numpy(), kind="stable"))]
         qu = unit_rows((centres[:40] + noise * OF.randn("grr:cq", (40, 256), CLUSTER_SEED)).to(gpu))
-        _clustered["idx"], _clustered["qu"] = fresh_index(gpu, rows, 5), qu
+        _clustered["idx"], _clustered["qu"] = fresh_index(gpu, rows, n=5), qu
     return _clustered["idx"], _clustered["qu"]
 
 

@@ -1,5 +1,6 @@
-"""GalleryIndex on the GPU: storage, the one-pass small-batch search against the dense P16 product (exact: same arithmetic, same
-product order) and against the CPU oracle, adversarial orders, incremental adds, the large-batch route and graph capture."""
+"""GalleryIndex on the GPU: storage, the one-pass small-batch search against the dense P16 product (gallery_support.dense_product;
+exact: same arithmetic, same product order) and against the CPU oracle, adversarial orders, incremental adds, the large-batch route
+and graph capture."""
 
 import pytest
 import torch
@@ -8,98 +9,32 @@ pytestmark = pytest.mark.gpu
 
 import oracle.evaluation as OE  # noqa: E402
 import oracle.fill as OF  # noqa: E402
+from gallery_support import c_search, dense_product, gpu, Inputs, same_values as same  # noqa: E402,F401
 
 SEED = 8  # every gap among the top k + 1 oracle values of every query is >= 2.1e-5 for the shapes below (checked on the CPU)
 SHAPES = [(1, 1, 1), (2, 10, 10), (5, 63, 5), (32, 64, 16), (7, 65, 10), (5, 4099, 16), (3, 8193, 10), (32, 8255, 10), (17, 20037, 10)]
 ADV_G = 20037
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
+IN = Inputs("gix:", SEED)
+raw = IN.raw
 
 
-def raw(Q, G):
-    return OF.randn("gix:q%d" % Q, (Q, 256), SEED), OF.randn("gix:g%d" % G, (G, 256), SEED)
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def query_panel(idx, q_unit, rows=32):
-    """the zero-padded P16 query panel, packed with the index's unit scalar as search packs it"""
-    from textreid_amd import ops
-
-    panel = torch.zeros(rows, 256, device=q_unit.device)
-    panel[: q_unit.shape[0]] = ops.p16_pack(q_unit.contiguous(), amax_=idx.unit_amax).data
-    return panel
-
-
-def dense_reference(idx, q_unit, k):
-    """the comparator: trid_gemm_p16 with the index's P16 gallery as A and the padded query panel as B -> [G, 32]; stable descending
-    sort of its transpose = (value descending, row ascending).  -> (values [Q,k], rows [Q,k]) on the CPU"""
-    from textreid_amd import ops
-
-    G, Q = len(idx), q_unit.shape[0]
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    sim = None
-    for cols in (32, 64):  # (a 64-row panel if the tile kernel declines 32 columns)
-        B = ops.P16(query_panel(idx, q_unit, cols), idx.unit_amax)
-        C = torch.empty(G, cols, device=q_unit.device)
-        try:
-            ops.gemm_p16(A, B, C, G, cols, 256, cols)
-        except RuntimeError:
-            continue
-        sim = C[:, :Q].t().contiguous().cpu()
-        break
-    assert sim is not None
+def top_k(sim, k):
+    """stable descending sort of the dense product = (value descending, row ascending) -> (values [Q,k], rows [Q,k]) on the CPU"""
     order = torch.sort(sim, dim=1, descending=True, stable=True)
     return order.values[:, :k].contiguous(), order.indices[:, :k].contiguous()
 
 
-def c_search(idx, q_unit, k, workgroups):
-    """trid_index_search_p16 itself, with a forced number of workers"""
-    from textreid_amd import lib as L
-    from textreid_amd.ops import _p, stream
-
-    Q, G = q_unit.shape[0], len(idx)
-    dev = q_unit.device
-    q16 = query_panel(idx, q_unit)
-    nws = L.load().trid_index_search_ws_bytes(G, Q, k, workgroups)
-    assert nws > 0
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    vals = torch.full((Q, k), float("nan"), device=dev)
-    rows = torch.full((Q, k), -7, dtype=torch.int64, device=dev)
-    L.call("trid_index_search_p16", _p(q16), _p(idx.rows_p16), _p(idx.unit_amax), Q, G, k, 0, _p(vals), _p(rows), _p(ws), workgroups, stream())
-    return vals.cpu(), rows.cpu()
-
-
-_built = {}
+def reference(idx, q_unit, k):
+    """the comparator: the top k of gallery_support.dense_product"""
+    return top_k(dense_product(idx, q_unit), k)
 
 
 def built(gpu, Q, G, k):
-    """index over the seed-8 gallery of G rows, the unit queries, the dense reference - computed once per shape"""
-    from textreid_amd import GalleryIndex
-
-    key = (Q, G, k)
-    if key not in _built:
-        te, ie = raw(Q, G)
-        idx = GalleryIndex()
-        assert idx.add(ie.to(gpu)) == 0 and len(idx) == G
-        qu = unit_rows(te.to(gpu))
-        _built[key] = (idx, te, ie, qu, dense_reference(idx, qu, k))
-    return _built[key]
-
-
-def same(got, ref, what):
-    gv, gr = got[0].cpu(), got[1].cpu()
-    assert torch.equal(gr, ref[1]), (what, "rows", gr, ref[1])
-    assert torch.equal(gv, ref[0]), (what, "values", float((gv - ref[0]).abs().max()))
+    """index over the seed-8 gallery of G rows (shared, never modified), the unit queries, the dense reference"""
+    idx, te, ie, qu, sim = IN.built(gpu, Q, G)
+    return idx, te, ie, qu, top_k(sim, k)
 
 
 # ----------------------------------------------------------------------------------------------------------- 1. storage
@@ -198,7 +133,7 @@ def test_adversarial_orders(gpu, kind):
     idx.add(g.to(gpu), normalize=False)
     assert torch.equal(idx.rows.cpu(), g)
     k = 10
-    ref = dense_reference(idx, qg, k)
+    ref = reference(idx, qg, k)
     if kind == "rising":
         assert ref[1][0].tolist() == list(range(ADV_G - 1, ADV_G - 1 - k, -1))
     if kind == "falling":

@@ -1,6 +1,6 @@
 """Row removal and filtered search of GalleryIndex on the GPU.  The comparator is exact: the dense trid_gemm_p16 product of the index's
-own P16 operands, disallowed rows at -inf, stable descending sort, rows of -inf values reported as -1 (gallery_mask_ref.masked_topk).
-Values and rows are compared bit for bit everywhere but in the one oracle test."""
+own P16 operands (gallery_support.dense_product), disallowed rows at -inf, stable descending sort, rows of -inf values reported as -1
+(gallery_mask_ref.masked_topk).  Values and rows are compared bit for bit everywhere but in the one oracle test."""
 
 import pytest
 import torch
@@ -10,127 +10,14 @@ pytestmark = pytest.mark.gpu
 import gallery_mask_ref as MR  # noqa: E402
 import oracle.evaluation as OE  # noqa: E402
 import oracle.fill as OF  # noqa: E402
+from gallery_support import c_search, dense_product, fresh_index, gpu, Inputs, same_values as same, unit_rows  # noqa: E402,F401
 
 SEED = 8
 SHAPES = [(1, 1, 1), (2, 33, 10), (5, 63, 5), (32, 64, 16), (7, 65, 10), (5, 4099, 16), (17, 20037, 10)]
 ADV_G = 20037
 NEG = float("-inf")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
-
-
-def raw(Q, G, seed=SEED):
-    return OF.randn("gmk:q%d" % Q, (Q, 256), seed), OF.randn("gmk:g%d" % G, (G, 256), seed)
-
-
-def coin(name, n, keep_of=2, seed=SEED):
-    """bool [n], true with probability 1 / keep_of (2: about half), drawn from the name (numpy RandomState)"""
-    return OF.randint("gmk:" + name, 0, keep_of, (n,), seed) == 0
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def query_panel(idx, q_unit, rows=32):
-    """the zero-padded P16 query panel, packed with the index's unit scalar as search packs it"""
-    from textreid_amd import ops
-
-    panel = torch.zeros(rows, 256, device=q_unit.device)
-    panel[: q_unit.shape[0]] = ops.p16_pack(q_unit.contiguous(), amax_=idx.unit_amax).data
-    return panel
-
-
-def dense_sim(idx, q_unit):
-    """trid_gemm_p16 with the index's P16 gallery (removed rows included) as A and zero-padded panels of 32 queries as B
-    -> sim [Q, G] on the CPU: the similarities the one-pass kernel must reproduce bit for bit"""
-    from textreid_amd import ops
-
-    G, Q = len(idx), q_unit.shape[0]
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    out = []
-    for at in range(0, Q, 32):
-        part = q_unit[at : at + 32]
-        sim = None
-        for cols in (32, 64):  # (a 64-row panel if the tile kernel declines 32 columns)
-            B = ops.P16(query_panel(idx, part, cols), idx.unit_amax)
-            C = torch.empty(G, cols, device=q_unit.device)
-            try:
-                ops.gemm_p16(A, B, C, G, cols, 256, cols)
-            except RuntimeError:
-                continue
-            sim = C[:, : part.shape[0]].t().contiguous().cpu()
-            break
-        assert sim is not None
-        out.append(sim)
-    return torch.cat(out, dim=0)
-
-
-def words_tensor(allow, device, extra=0):
-    """the comparator's packed words (made on the CPU, NOT by the pack kernel) as the int32 device buffer the C entry point reads"""
-    w = MR.pack_words(allow)
-    w = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
-    if extra:
-        w = torch.cat([w, torch.full((extra,), -1, dtype=torch.int32)])
-    return w.to(device)
-
-
-def c_search(idx, q_unit, k, workgroups, allow=None):
-    """trid_index_search_masked_p16 itself (allow None: trid_index_search_p16), with a forced number of workers"""
-    from textreid_amd import lib as L
-    from textreid_amd.ops import _p, stream
-
-    Q, G = q_unit.shape[0], len(idx)
-    dev = q_unit.device
-    q16 = query_panel(idx, q_unit)
-    nws = L.load().trid_index_search_ws_bytes(G, Q, k, workgroups)
-    assert nws > 0
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    vals = torch.full((Q, k), float("nan"), device=dev)
-    rows = torch.full((Q, k), -7, dtype=torch.int64, device=dev)
-    if allow is None:
-        L.call("trid_index_search_p16", _p(q16), _p(idx.rows_p16), _p(idx.unit_amax), Q, G, k, 0, _p(vals), _p(rows), _p(ws), workgroups, stream())
-    else:
-        words = words_tensor(allow, dev)
-        assert words.numel() == (G + 31) // 32  # exactly the words the contract names: nothing beyond them may be read
-        L.call("trid_index_search_masked_p16", _p(q16), _p(idx.rows_p16), _p(idx.unit_amax), _p(words), Q, G, k, 0, _p(vals), _p(rows), _p(ws),
-               workgroups, stream())
-    return vals.cpu(), rows.cpu()
-
-
-def fresh_index(gpu, ie, pids=None, **kw):
-    from textreid_amd import GalleryIndex
-
-    idx = GalleryIndex()
-    assert idx.add(ie.to(gpu), pids=pids, **kw) == 0 and len(idx) == ie.shape[0]
-    return idx
-
-
-_built = {}
-
-
-def built(gpu, Q, G):
-    """index over the seed-8 gallery of G rows (never modified by a test), the raw and unit queries, the dense similarities"""
-    key = (Q, G)
-    if key not in _built:
-        te, ie = raw(Q, G)
-        idx = fresh_index(gpu, ie)
-        qu = unit_rows(te.to(gpu))
-        _built[key] = (idx, te, ie, qu, dense_sim(idx, qu))
-    return _built[key]
-
-
-def same(got, ref, what):
-    gv, gr = got[0].cpu(), got[1].cpu()
-    assert torch.equal(gr, ref[1]), (what, "rows", gr, ref[1])
-    assert torch.equal(gv, ref[0]), (what, "values", gv, ref[0])
+IN = Inputs("gmk:", SEED)
+raw, coin, built = IN.raw, IN.coin_keep, IN.built  # (built: the index is shared and never modified by a test)
 
 
 # ----------------------------------------------------------------------------------------------------------- 1. pack kernel
@@ -244,7 +131,7 @@ def test_ties_the_higher_copy_takes_the_place_of_the_removed_lower_copy(gpu):
     qg = q.to(gpu)
     idx = fresh_index(gpu, g, normalize=False)
     k = 10
-    sim = dense_sim(idx, qg)
+    sim = dense_product(idx, qg)
     before = MR.masked_topk(sim, torch.ones(ADV_G, dtype=torch.bool), k)
     same(idx.search(qg, k=k, normalize=False), before, "ties, nothing removed")
     r = before[1]
@@ -267,7 +154,7 @@ def test_rising_every_other_row_removed(gpu):
     qg = q.to(gpu)
     idx = fresh_index(gpu, g, normalize=False)
     k = 10
-    sim = dense_sim(idx, qg)
+    sim = dense_product(idx, qg)
     gone = torch.arange(0, ADV_G, 2)
     assert idx.remove(rows=gone.to(gpu)) == gone.numel()
     allow = torch.ones(ADV_G, dtype=torch.bool)
@@ -313,7 +200,7 @@ def test_lifecycle_remove_add_pids_compact_state_dict(gpu):
     n = G + 40
     allow = torch.cat([allow, torch.ones(40, dtype=torch.bool)])
     assert len(idx) == n and idx.live_count == int(allow.sum()) and torch.equal(idx.live.cpu(), allow)
-    sim2 = dense_sim(idx, qu)
+    sim2 = dense_product(idx, qu)
     assert torch.equal(sim2[:, :G], sim)
     ref2 = MR.masked_topk(sim2, allow, k)
     same(idx.search(qu, k=k, normalize=False), ref2, "add after remove")
@@ -398,7 +285,7 @@ def test_more_than_32_queries_run_in_masked_panels(gpu):
     te, ie = raw(Q, G)
     idx = fresh_index(gpu, ie)
     qu = unit_rows(te.to(gpu))
-    sim = dense_sim(idx, qu)
+    sim = dense_product(idx, qu)
     dead = coin("big_dead", G, 10)
     assert idx.remove(rows=torch.nonzero(dead).reshape(-1)) == int(dead.sum())
     m = coin("big_mask", G)

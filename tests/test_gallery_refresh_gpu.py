@@ -13,16 +13,11 @@ import gallery_nn_update_ref as NU  # noqa: E402
 import gallery_rerank_ref as RR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
-from test_gallery_rerank_gpu import dense_product, gallery, queries  # noqa: E402
+from gallery_support import dense_product, gpu, Inputs  # noqa: E402,F401
 
 SEED = 13
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
+IN = Inputs("grr:", SEED)  # (the galleries and queries of test_gallery_rerank_gpu.py, by name: the cached galleries are shared with it)
+gallery, queries, product_of = IN.gallery, IN.queries, IN.product_of
 
 
 def built_index(gpu, rows, n, capacity=0):
@@ -141,23 +136,13 @@ def test_merge_kernel_equals_the_reference_and_touches_nothing_else(gpu, rows, m
 
 
 # ------------------------------------------------------------------------------------------------------------------ the wide product
-_products = {}
-
-
-def self_product(gpu, idx, key):
-    """the [len, len] narrow dense product of an index's rows against themselves (numpy), once per key"""
-    if key not in _products:
-        _products[key] = dense_product(idx, idx.rows).numpy()
-    return _products[key]
-
-
 @pytest.mark.parametrize("n0", [20, 60, 65, 2000, 2048])  # (20 / 60 / 65: the 256x32, 128x64 and 128x128 tiles; 2048: the streaming kernel's shape)
 def test_wide_candidate_product_equals_the_narrow_dense_product(gpu, n0):
     from textreid_amd import GalleryIndex
 
     idx = GalleryIndex()
     idx.add(gallery(n0 + 32).to(gpu))
-    sim = self_product(gpu, idx, ("wide", n0))  # sim[i, g]: row i as the query (B panel), row g as the gallery (A)
+    sim = product_of(idx, ("wide", n0))  # sim[i, g]: row i as the query (B panel), row g as the gallery (A)
     cand = idx._candidate_scores(n0, 32, n0)
     wide = cand.reshape(-1)[: 32 * n0].reshape(32, n0).cpu().numpy()
     want = np.ascontiguousarray(sim[:n0, n0:].T)
@@ -184,7 +169,7 @@ def test_refresh_after_add_equals_rebuild_and_the_dense_product(gpu, n0, added):
         fresh = built_index(gpu, rows, n)
         same_graph(idx, fresh, (n0, added, n))
         if sim is None:
-            sim = self_product(gpu, idx, ("add", n0, added))
+            sim = product_of(idx, ("add", n0, added))
         want = RR.graph(sim, n)
         assert np.array_equal(idx.neighbours.cpu().numpy(), want), (n0, added, n)
         want_val = np.take_along_axis(sim, want.astype(np.int64), axis=1)  # the product's own entries: s(query i, gallery g)

@@ -12,103 +12,16 @@ pytestmark = pytest.mark.gpu
 import gallery_rerank_ref as RR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
+from gallery_support import dense_product, fresh_index, gpu, Inputs, same_bits as same, unit_rows  # noqa: E402,F401
 
 SEED = 13
 # the clustered gallery's generator seed: with 13 the CPU trial of the recipe (fp32 matmul) left ONE pair with c = 5, which a last-bit
 # difference of the P16 product could remove; 15 leaves 7 (c = 1 .. 5: 392 / 84 / 84 / 48 / 7, 29 of 40 orders and 10 of 40 sets
 # changed at k = 10).  The noise factor stays at 2.0 and the two conditions are asserted as they stand.
 CLUSTER_SEED = 15
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def dense_product(idx, q_unit):
-    """-> fp32 [Q, len] on the host: trid_gemm_p16 with the index's P16 gallery as A and the zero-padded query panel (32 queries at a
-    time, packed with the index's unit scalar as search packs it) as B - 64 panel rows if the tile kernel declines 32 columns"""
-    from textreid_amd import ops
-
-    G, dev = len(idx), q_unit.device
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    out = []
-    for at in range(0, q_unit.shape[0], 32):
-        part = q_unit[at : at + 32].contiguous()
-        sim = None
-        for cols in (32, 64):
-            panel = torch.zeros(cols, 256, device=dev)
-            panel[: part.shape[0]] = ops.p16_pack(part, amax_=idx.unit_amax).data
-            C = torch.empty(G, cols, device=dev)
-            try:
-                ops.gemm_p16(A, ops.P16(panel, idx.unit_amax), C, G, cols, 256, cols)
-            except RuntimeError:
-                continue
-            sim = C[:, : part.shape[0]].t().contiguous().cpu()
-            break
-        assert sim is not None
-        out.append(sim)
-    return torch.cat(out, dim=0)
-
-
-def same(got, want, what=""):
-    assert TR.same((got[0].cpu().numpy(), got[1].cpu().numpy()), (np.asarray(want[0]), np.asarray(want[1]))), what
-
-
-def coin(name, n, one_in=2):
-    return OF.randint("grr:" + name, 0, one_in, (n,), SEED) != 0 if one_in == 2 else OF.randint("grr:" + name, 0, one_in, (n,), SEED) == 0
-
-
-_built = {}
-
-
-def gallery(G):
-    if G not in _built:
-        _built[G] = OF.randn("grr:g%d" % G, (G, 256), SEED)
-    return _built[G]
-
-
-def fresh_index(gpu, rows, n=None):
-    from textreid_amd import GalleryIndex
-
-    idx = GalleryIndex()
-    idx.add(rows.to(gpu))
-    if n is not None:
-        idx.build_neighbours(n)
-    return idx
-
-
-_indexes = {}
-
-
-def shared_index(gpu, G, n=5):
-    """one index with a built graph per (length, n), never modified by the tests that share it"""
-    if (G, n) not in _indexes:
-        _indexes[G, n] = fresh_index(gpu, gallery(G), n)
-    return _indexes[G, n]
-
-
-_products = {}
-
-
-def self_product(gpu, G):
-    """the [G, G] dense product of gallery(G) against itself (numpy), computed once: it depends on the rows alone"""
-    if G not in _products:
-        idx = shared_index(gpu, G)
-        _products[G] = dense_product(idx, idx.rows).numpy()
-    return _products[G]
-
-
-def queries(gpu, Q, tag="q"):
-    return unit_rows(OF.randn("grr:%s%d" % (tag, Q), (Q, 256), SEED).to(gpu))
+IN = Inputs("grr:", SEED, graph_n=5)  # (test_gallery_refresh_gpu.py and test_gallery_expand_gpu.py name the same inputs and share the caches)
+coin, gallery, queries = IN.coin_one_in, IN.gallery, IN.queries
+shared_index, self_product = IN.shared_index, IN.self_product  # (one index with a built graph per (length, n), never modified by a test)
 
 
 def reference(idx, sim, k, alpha=0.05, allow=None):
@@ -228,7 +141,7 @@ def test_sampled_graph_at_20037_rows(gpu):
 
 def test_duplicates_start_with_the_lowest_numbered_copy(gpu):
     base = gallery(2000)[:300]
-    idx = fresh_index(gpu, torch.cat([base, base, base], dim=0), 5)  # row r, r + 300, r + 600 are one image
+    idx = fresh_index(gpu, torch.cat([base, base, base], dim=0), n=5)  # row r, r + 300, r + 600 are one image
     nn = idx.neighbours.cpu()
     r = torch.arange(900) % 300
     assert torch.equal(nn[:, 0].long(), r) and torch.equal(nn[:, 1].long(), r + 300) and torch.equal(nn[:, 2].long(), r + 600)
@@ -315,7 +228,7 @@ def test_clustered_gallery_where_the_term_bites(gpu):
     rows = centres.repeat_interleave(8, dim=0) + noise * OF.randn("grr:cnoise", (2000, 256), CLUSTER_SEED)
     rows = rows[torch.from_numpy(np.argsort(OF.randn("grr:cperm", (2000,), CLUSTER_SEED).numpy(), kind="stable"))]
     qu = unit_rows((centres[:40] + noise * OF.randn("grr:cq", (40, 256), CLUSTER_SEED)).to(gpu))
-    idx = fresh_index(gpu, rows, n)
+    idx = fresh_index(gpu, rows, n=n)
     sim = dense_product(idx, qu).numpy()
     gnn = RR.graph(dense_product(idx, idx.rows).numpy(), n)
     assert np.array_equal(idx.neighbours.cpu().numpy(), gnn)
@@ -440,7 +353,7 @@ def test_state_dict_round_trip_and_growth(gpu):
     from textreid_amd import GalleryIndex
 
     rows = gallery(2000)
-    idx = fresh_index(gpu, rows[:300], 5)
+    idx = fresh_index(gpu, rows[:300], n=5)
     qu = queries(gpu, 5)
     k = 64
     same(idx.search_reranked(qu, k=k, normalize=False), reference(idx, dense_product(idx, qu), k), "first")

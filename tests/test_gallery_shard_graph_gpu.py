@@ -2,7 +2,8 @@
 reference (gallery_shard_graph_ref.merge; over-allocated buffers compared whole, so that nothing outside the named slots moves), the
 in-process form against ONE GalleryIndex over the same rows (build_neighbours, search_reranked, search_reranked_pids,
 refresh_neighbours against a fresh build, state_dict, capture), and the by-rank form on two gloo ranks sharing the GPU
-(tests/gallery_shard_graph_worker.py).  Nothing here needs a tolerance: values are compared as bit patterns, ids exactly."""
+(tests/gallery_shard_graph_worker.py, started by rank_launch.run_ranks).  The pair of the two is gallery_support.ShardPair with add /
+remove / same_graph / build on top.  Nothing here needs a tolerance: values are compared as bit patterns, ids exactly."""
 
 import numpy as np
 import pytest
@@ -11,16 +12,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gallery_shard_graph_ref as SG  # noqa: E402
-from test_gallery_shards_gpu import _run_ranks  # noqa: E402
+from gallery_support import ShardPair, gpu, shard_inputs  # noqa: E402,F401
+from rank_launch import run_ranks  # noqa: E402
 
 STRIDE = SG.SHARD_STRIDE
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
 
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel alone
@@ -125,30 +120,13 @@ def test_merge_kernel_equals_the_reference_and_touches_nothing_else(gpu, rows, m
 
 
 # ------------------------------------------------------------------------------------------------------------------ the host path
-def _inputs(kind, G, extra):
-    """G + extra gallery rows, 40 queries, pids: exact-level rows (12 base rows repeated: exact ties across every cut, the values of
-    test_gallery_shards_gpu) or unit random rows"""
-    gen = torch.Generator().manual_seed(41 + G)
-    pids = torch.randint(0, (G + extra) // 4, (G + extra,), generator=gen)
-    if kind == "ties":
-        lv = torch.tensor([-1.0, -0.5, 0.0, 0.5, 1.0]) / 8
-        q = lv[torch.randint(0, 5, (40, 256), generator=gen)]
-        base = lv[torch.randint(0, 5, (12, 256), generator=gen)]
-        return q, base[torch.randint(0, 12, (G + extra,), generator=gen)], pids, False
-    q = torch.nn.functional.normalize(torch.randn(40, 256, generator=gen), dim=1)
-    return q, torch.nn.functional.normalize(torch.randn(G + extra, 256, generator=gen), dim=1), pids, True
-
-
-class Pair:
+class Pair(ShardPair):
     """ONE GalleryIndex and one GalleryShards over the same rows, appended in the same order (so every part but the last is full),
     and the comparisons between them"""
 
     def __init__(self, kind, gpu, G, shard_rows, extra=100):
-        from textreid_amd import GalleryIndex, GalleryShards
-
-        q, g, pids, self.normalize = _inputs(kind, G, extra)
-        self.q, self.g, self.pids = q.to(gpu), g.to(gpu), pids.to(gpu)
-        self.one, self.sh, self.shard_rows = GalleryIndex(), GalleryShards(shard_rows=shard_rows), shard_rows
+        # G + extra gallery rows, 40 queries, about four rows per pid: the exact-level rows of test_gallery_shards_gpu or unit random rows
+        super().__init__(gpu, shard_inputs(kind, 41 + G, 40, G + extra, (G + extra) // 4), shard_rows)
         self.at = 0
         self.add(G)
 
@@ -165,13 +143,6 @@ class Pair:
             rows = torch.as_tensor(rows, dtype=torch.int64)
             assert self.sh.remove(rows=self.to_global(rows)) == self.one.remove(rows=rows)
         assert self.sh.live_count == self.one.live_count
-
-    def to_global(self, rows):
-        rows = rows.long()
-        return torch.where(rows < 0, rows, (rows // self.shard_rows) * STRIDE + rows % self.shard_rows)
-
-    def split(self, mask):
-        return [mask[at : at + self.shard_rows] for at in range(0, len(self.one), self.shard_rows)]
 
     def same_graph(self, what=""):
         """the shards' lists and values against the ONE index's, as they stand"""
@@ -198,11 +169,7 @@ class Pair:
         want = getattr(one, name)(q, k=kk, alpha=alpha, normalize=self.normalize, mask=mask)
         what = (name, Q, k, alpha)
         assert len(got) == len(want) and all(tuple(t.shape) == (Q, k) for t in got), what
-        assert torch.equal(got[0][:, :kk].view(torch.int32), want[0].view(torch.int32)), what + ("values",)
-        assert torch.equal(got[1][:, :kk], self.to_global(want[1])), what + ("rows",)
-        if len(got) == 3:
-            assert torch.equal(got[2][:, :kk], want[2]), what + ("pids",)
-        assert bool(torch.isneginf(got[0][:, kk:]).all()) and all(bool((t[:, kk:] == -1).all()) for t in got[1:]), what + ("tail",)
+        self.compare(got, want, kk, what)
         return got
 
 
@@ -435,4 +402,4 @@ def test_recorded_search_reranked_replays_against_new_queries(pair):
 def test_two_ranks():
     """200 | 100 rows and 300 | 0 rows: build_neighbours and both re-ranked searches equal the one-process GalleryIndex on both ranks -
     see tests/gallery_shard_graph_worker.py"""
-    _run_ranks(2, "gallery_shard_graph_worker.py", ("SHARD_GRAPH_UNEVEN_OK", "SHARD_GRAPH_EMPTY_OK"))
+    run_ranks(2, "gallery_shard_graph_worker.py", ("SHARD_GRAPH_UNEVEN_OK", "SHARD_GRAPH_EMPTY_OK"), 240, TRID_DIST_BACKEND="gloo")

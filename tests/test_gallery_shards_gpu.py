@@ -1,11 +1,7 @@
 """GalleryShards on the GPU: trid_index_merge_lists_f32 against the numpy reference (gallery_shards_ref) bit for bit, the in-process
 form against ONE GalleryIndex over the same rows (values bit for bit, rows after mapping, pids), and the by-rank form on two gloo
-ranks sharing the GPU (tests/gallery_shards_worker.py).  Nothing here needs a tolerance."""
-
-import os
-import socket
-import subprocess
-import sys
+ranks sharing the GPU (tests/gallery_shards_worker.py, started by rank_launch.run_ranks).  The pair of the two is
+gallery_support.ShardPair with this file's order of adds and its choice of comparator method.  Nothing here needs a tolerance."""
 
 import numpy as np
 import pytest
@@ -14,16 +10,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gallery_shards_ref as SR  # noqa: E402
+from gallery_support import ShardPair, gpu, shard_inputs  # noqa: E402,F401
+from rank_launch import run_ranks  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G, SHARD = 300, 96  # parts of 96, 96, 96 and 12 rows
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
 
 
 # ------------------------------------------------------------------ the kernel
@@ -88,41 +78,15 @@ def test_merge_in_rounds_equals_one_merge(gpu):
 
 
 # ------------------------------------------------------------------ the in-process form
-def _inputs(kind):
-    gen = torch.Generator().manual_seed(19)
-    pids = torch.randint(0, 70, (G,), generator=gen)  # (every pid about four times: reused across the parts)
-    if kind == "ties":
-        # the exact-arithmetic levels of _tie_inputs (test_rank_shard_gpu.py); 12 base rows repeated: exact ties straddle every cut
-        lv = torch.tensor([-1.0, -0.5, 0.0, 0.5, 1.0]) / 8
-        q = lv[torch.randint(0, 5, (33, 256), generator=gen)]
-        base = lv[torch.randint(0, 5, (12, 256), generator=gen)]
-        return q, base[torch.randint(0, 12, (G,), generator=gen)], pids, False
-    q = torch.nn.functional.normalize(torch.randn(33, 256, generator=gen), dim=1)
-    return q, torch.nn.functional.normalize(torch.randn(G, 256, generator=gen), dim=1), pids, True
-
-
-class Pair:
+class Pair(ShardPair):
     """one GalleryIndex and one GalleryShards (shard_rows = 96) over the same 300 rows, and the comparison between them"""
 
     def __init__(self, kind, gpu, shard_rows=SHARD):
-        from textreid_amd import GalleryIndex, GalleryShards
-
-        q, g, pids, self.normalize = _inputs(kind)
-        self.q, self.g, self.pids = q.to(gpu), g.to(gpu), pids.to(gpu)
-        self.one = GalleryIndex()
+        # 33 queries, pids in [0, 70): every pid about four times, reused across the parts
+        super().__init__(gpu, shard_inputs(kind, 19, 33, G, 70), shard_rows)
         self.one.add(self.g, self.pids, normalize=self.normalize)
-        self.sh = GalleryShards(shard_rows=shard_rows)
         # (one add call spanning three parts, then one that fills the third and opens the fourth)
         self.first = [self.sh.add(self.g[:250], self.pids[:250], normalize=self.normalize), self.sh.add(self.g[250:], self.pids[250:], normalize=self.normalize)]
-        self.shard_rows = shard_rows
-
-    def to_global(self, rows):
-        from textreid_amd.index_shards import SHARD_STRIDE
-
-        return torch.where(rows < 0, rows, (rows // self.shard_rows) * SHARD_STRIDE + rows % self.shard_rows)
-
-    def split(self, mask):
-        return [mask[at : at + self.shard_rows] for at in range(0, G, self.shard_rows)]
 
     def check(self, name, Q, k, mask=None, sh=None):
         """sh.<name>(k) against the plain index at k' = min(k, what it can give), padded with absent slots"""
@@ -139,13 +103,7 @@ class Pair:
             want = getattr(one, "shortlist_pids" if distinct else "shortlist")(q, k=kk, normalize=self.normalize, mask=mask)
         else:
             want = getattr(one, name)(q, k=kk, normalize=self.normalize, mask=mask)
-        what = (name, Q, k)
-        if want is not None:
-            assert torch.equal(got[0][:, :kk].view(torch.int32), want[0].view(torch.int32)), what + ("values",)
-            assert torch.equal(got[1][:, :kk], self.to_global(want[1])), what + ("rows",)
-            if distinct:
-                assert torch.equal(got[2][:, :kk], want[2]), what + ("pids",)
-        assert bool(torch.isneginf(got[0][:, kk:]).all()) and all(bool((t[:, kk:] == -1).all()) for t in got[1:]), what + ("tail",)
+        self.compare(got, want, kk, (name, Q, k))
         return got
 
 
@@ -298,32 +256,6 @@ def test_recorded_searches_replay_against_new_queries(pair):
 
 
 # ------------------------------------------------------------------ two ranks
-def _run_ranks(world, worker, need, timeout=240):
-    """the launcher of test_rank_shard_gpu.py::_run_ranks, restated: fresh child processes on 127.0.0.1, one per rank, killed if
-    they outlive the time limit, every exit status checked"""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   OMP_NUM_THREADS="8", HSA_ENABLE_IPC_MODE_LEGACY="0", TRID_DIST_BACKEND="gloo")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    try:
-        outs = [p.communicate(timeout=timeout)[0] for p in procs]
-    finally:
-        for p in procs:  # (exactly the processes started here)
-            if p.poll() is None:
-                p.kill()
-    for p, o in zip(procs, outs):
-        assert p.returncode == 0, o[-3000:]
-    assert all(tag in outs[0] for tag in need), outs[0][-3000:]
-
-
 def test_two_ranks():
     """200 | 100 rows and 300 | 0 rows: the four searches equal the one-process GalleryIndex on both ranks - see tests/gallery_shards_worker.py"""
-    _run_ranks(2, "gallery_shards_worker.py", ("SHARDS_UNEVEN_OK", "SHARDS_EMPTY_OK"))
+    run_ranks(2, "gallery_shards_worker.py", ("SHARDS_UNEVEN_OK", "SHARDS_EMPTY_OK"), 240, TRID_DIST_BACKEND="gloo")

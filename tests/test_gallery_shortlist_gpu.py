@@ -1,9 +1,8 @@
 """GalleryIndex.shortlist on the GPU.  The comparator is the dense trid_gemm_p16 product of the index's OWN operands (P16 gallery as A,
-the zero-padded query panel as B, unit scale) read back to the host, then topk_deep_ref over the allowed rows (gallery_mask_ref's
+the zero-padded query panel as B, unit scale: gallery_support.dense_product) read back to the host, then topk_deep_ref over the allowed rows (gallery_mask_ref's
 masked_topk turns a real -inf into an absent row, so it only serves where no score is -inf: it is used as a cross-check).  Nothing
 here needs a tolerance: values are compared as bit patterns, rows exactly."""
 
-import numpy as np
 import pytest
 import torch
 
@@ -12,47 +11,11 @@ pytestmark = pytest.mark.gpu
 import gallery_mask_ref as MR  # noqa: E402
 import oracle.fill as OF  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
+from gallery_support import dense_product, fresh_index, gpu, Inputs, same_bits as same, unit_rows  # noqa: E402,F401
 
 SEED = 12
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
-
-
-def unit_rows(x):
-    from textreid_amd import ops
-
-    return ops.l2norm_rows(x.contiguous())[0]
-
-
-def dense_product(idx, q_unit):
-    """-> fp32 [Q, len] on the host: trid_gemm_p16 with the index's P16 gallery as A and the zero-padded query panel (32 queries at a
-    time, packed with the index's unit scalar as search packs it) as B - 64 panel rows if the tile kernel declines 32 columns"""
-    from textreid_amd import ops
-
-    G, dev = len(idx), q_unit.device
-    A = ops.P16(idx.rows_p16, idx.unit_amax)
-    out = []
-    for at in range(0, q_unit.shape[0], 32):
-        part = q_unit[at : at + 32].contiguous()
-        sim = None
-        for cols in (32, 64):
-            panel = torch.zeros(cols, 256, device=dev)
-            panel[: part.shape[0]] = ops.p16_pack(part, amax_=idx.unit_amax).data
-            C = torch.empty(G, cols, device=dev)
-            try:
-                ops.gemm_p16(A, ops.P16(panel, idx.unit_amax), C, G, cols, 256, cols)
-            except RuntimeError:
-                continue
-            sim = C[:, : part.shape[0]].t().contiguous().cpu()
-            break
-        assert sim is not None
-        out.append(sim)
-    return torch.cat(out, dim=0)
+IN = Inputs("gsl:", SEED)
+coin, gallery, queries, shared_index = IN.coin_one_in, IN.gallery, IN.queries, IN.shared_index  # (a shared index is never modified by a test)
 
 
 def reference(sim, k, allow=None):
@@ -61,45 +24,6 @@ def reference(sim, k, allow=None):
         mv, mr = MR.masked_topk(sim, torch.ones(sim.shape[1], dtype=torch.bool) if allow is None else allow, k)
         assert TR.same((mv.numpy(), mr.numpy()), (vals, rows))
     return vals, rows
-
-
-def same(got, want, what=""):
-    assert TR.same((got[0].cpu().numpy(), got[1].cpu().numpy()), (np.asarray(want[0]), np.asarray(want[1]))), what
-
-
-def coin(name, n, one_in=2):
-    return OF.randint("gsl:" + name, 0, one_in, (n,), SEED) != 0 if one_in == 2 else OF.randint("gsl:" + name, 0, one_in, (n,), SEED) == 0
-
-
-_built = {}
-
-
-def gallery(G):
-    if G not in _built:
-        _built[G] = OF.randn("gsl:g%d" % G, (G, 256), SEED)
-    return _built[G]
-
-
-def fresh_index(gpu, rows, pids=None):
-    from textreid_amd import GalleryIndex
-
-    idx = GalleryIndex()
-    idx.add(rows.to(gpu), pids=pids)
-    return idx
-
-
-_indexes = {}
-
-
-def shared_index(gpu, G):
-    """one index per length, never modified by the tests that share it"""
-    if G not in _indexes:
-        _indexes[G] = fresh_index(gpu, gallery(G))
-    return _indexes[G]
-
-
-def queries(gpu, Q, tag="q"):
-    return unit_rows(OF.randn("gsl:%s%d" % (tag, Q), (Q, 256), SEED).to(gpu))
 
 
 # ------------------------------------------------------------------------------------------------------------------ shapes

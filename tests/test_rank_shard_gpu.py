@@ -5,26 +5,15 @@ the ranks equal the fp64 restatement tests/rank_stream_ref.py exactly.  Two rank
 GPU over gloo): evaluation.positive_ranks_sharded / rank_from_embeddings_sharded / tables_sharded against the one-process
 results."""
 
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 import torch
 
 import rank_stream_ref as R
+from gallery_support import gpu  # noqa: F401
+from rank_launch import run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = 20011
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
 
 
 def _tie_inputs(G):
@@ -174,35 +163,9 @@ def test_sharded_rerank_fix(ties, nn):
     assert torch.equal(_p16_counts(ties, [9001, 11010], nn) + 1, want[2])
 
 
-def _run_ranks(world, worker, need, timeout=300, **extra_env):
-    """test_dp_gpu.py::_run_ranks: fresh child processes, one per rank, killed if they outlive the time limit"""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   OMP_NUM_THREADS="8", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    try:
-        outs = [p.communicate(timeout=timeout)[0] for p in procs]
-    finally:
-        for p in procs:  # (exactly the processes started here)
-            if p.poll() is None:
-                p.kill()
-    for p, o in zip(procs, outs):
-        assert p.returncode == 0, o[-3000:]
-    assert all(tag in outs[0] for tag in need), outs[0][-3000:]
-    return outs[0]
-
-
 def test_two_ranks():
     """(a) ties over 9001 | 11010, plain and re-ranked; (d) 20011 | 0; (b) random unit rows inside the fp64 brackets and equal to
     the one-process ranks; (c) 9001 | 5000 on the panel path; (e) the four tables on the golden embeddings; (f) no [Q, G_local]
     allocation - see tests/rank_shard_worker.py"""
-    _run_ranks(2, "rank_shard_worker.py", ("SHARD_TIES_OK", "SHARD_EMPTY_OK", "SHARD_RANDOM_OK", "SHARD_PANEL_OK", "SHARD_TABLES_OK",
-                                           "SHARD_ALLOC_OK"), TRID_DIST_BACKEND="gloo")
+    run_ranks(2, "rank_shard_worker.py", ("SHARD_TIES_OK", "SHARD_EMPTY_OK", "SHARD_RANDOM_OK", "SHARD_PANEL_OK", "SHARD_TABLES_OK",
+                                          "SHARD_ALLOC_OK"), 300, TRID_DIST_BACKEND="gloo")

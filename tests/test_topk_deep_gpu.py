@@ -8,16 +8,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-import gallery_mask_ref as MR  # noqa: E402
 import oracle.evaluation as OE  # noqa: E402
 import topk_deep_ref as TR  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda")
+from gallery_support import gpu, words_tensor  # noqa: E402,F401
 
 
 def lib():
@@ -37,15 +30,6 @@ def matrix(Q, G, seed, ties=False):
         pool = np.array([0.0, -0.0, 0.25, -0.25, 1.0, 3.5, -2.0], dtype=np.float32)
         return pool[rng.randint(0, pool.size, size=(Q, G))]
     return rng.standard_normal((Q, G)).astype(np.float32)
-
-
-def words_tensor(allowed, dev, garbage=False):
-    """bool [G] -> the int32 device tensor of trid_index_pack_mask_u32's words; garbage: the bits of columns >= G in the last word set"""
-    w = MR.pack_words(torch.as_tensor(np.asarray(allowed))).numpy().astype(np.uint64)
-    G = len(allowed)
-    if garbage and G % 32:
-        w[-1] |= np.uint64((0xFFFFFFFF << (G % 32)) & 0xFFFFFFFF)
-    return torch.from_numpy(w.astype(np.uint32).view(np.int32).copy()).to(dev)
 
 
 def deep(dev_sim, Q, G, k, ld_q, ld_g, words=None, offset=0, chunk=0):
